@@ -20,6 +20,15 @@ consecutive ranks into one tensor-parallel replica (RCCL all-reduce).
 exits with its status; inside one, WORLD_SIZE must equal N.
 
 Prints ONE JSON line on rank 0 (metric contract: BASELINE.json / SURVEY.md §8d).
+
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the timed steps, the result line.  `--full` adds, after the timed loop, every
+measurement that takes runs of its own: the roofline candidates (`roofline`,
+`roofline_2`), the collectives' share under `--tp` (`tp_collective`) and the
+CPU oracle sample (`cpu_baseline`).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float32), for an output-for-output
+comparison of two builds: the inputs are seeded, the same arguments give the
+same inputs.
 """
 import argparse
 import ctypes
@@ -53,8 +62,14 @@ def parse():
                     help="prompt length in tokens: a long script prefilled through the product path "
                          "(k_attn_pf + k_gemm_xl) before timing decode at that context "
                          "(SURVEY.md §8d config 5: 64K-position decode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-tokens", type=int, default=8, help="timed tokens of the CPU oracle sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop also measure the roofline candidates (isolated graph replays), the "
+                         "collectives' share under --tp and the CPU oracle sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (audio frame, acoustic latents, constrained "
+                         "logits of every dialogue of rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU oracle sample out")
+    ap.add_argument("--cpu-tokens", type=int, default=8, help="timed tokens of the CPU oracle sample (--full)")
     ap.add_argument("--plumbing", action="store_true",
                     help="tests only: run the launch / barrier / max-over-ranks / JSON path with an empty step "
                          "(no engine; works on a CPU host over gloo)")
@@ -669,6 +684,35 @@ def throughput(dt, batch, steps, world):
     return tps, tps * HOP / SR
 
 
+# ------------------------------------------------------------------ outputs of the last timed step
+DUMP_MAX_BYTES = 64_000_000    # all files of one --dump-outputs together
+
+
+def last_step_outputs(sess):
+    """What the last step of the loop handed to its caller, one row per dialogue
+    of the session: `audio`, the 3,200-sample frame appended to each dialogue's
+    speech output; `latents`, the acoustic latents the diffusion head sampled
+    for that frame; `logits`, the constrained scores (speech_start, speech_end,
+    speech_diffusion, eos) the step's token choice read back."""
+    torch.cuda.synchronize()
+    return dict(audio=torch.cat([c[-1] for c in sess.audio_chunks], 0), latents=sess.noise_dev[:sess.B],
+                logits=sess.logits_pin)
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every tensor of `arrays` as path/<name>.npy in float32.
+    An array above its share of max_bytes is cut to a fixed seeded sample of
+    its elements (the same elements in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (max_bytes // len(arrays) - 128) // 4      # elements per file, beside its .npy header
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # ------------------------------------------------------------------ main
 def main():
     args = parse()
@@ -728,48 +772,51 @@ def main():
     wb = weight_bytes(model.engine.w, B, S)
     ctx_avg = (ctx0 + ctx1) / 2
     bpt = bytes_per_token(wb, model.config, B, S, ctx_avg, (ctx0 + ctx1) / 2 - L)
-    # `roofline` = whichever of the two candidates (the LM MLP block, the head FFN
-    # layer) takes more time per step (avg x launches per step), i.e. the top row
-    # of the step profile (profiles/r06_steps_b1.txt); the other is `roofline_2`
-    try:   # the LM MLP block in one launch (B = 1), else the LM gate|up GEMV
-        roof_lm = measure_lm_ffn(model, B)
-    except Exception as e:   # noqa: BLE001
-        print(f"bench: LM MLP block roofline not measured: {e}", file=sys.stderr, flush=True)
-        roof_lm = None
-    roof_lm = roof_lm or measure_gemv(model, B)
-    roof_head = None
-    if world == 1 or T == 1:
-        try:
-            roof_head = measure_head_layers(model, B)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(sess))
+    model.engine.check_sync()   # a grid wait that gave up in the loop is an error, not a result
+    roofline = roofline_2 = tp_coll = cpu = None
+    if args.full:
+        # `roofline` = whichever of the two candidates (the LM MLP block, the head FFN
+        # layer) takes more time per step (avg x launches per step), i.e. the top row
+        # of the step profile (profiles/r06_steps_b1.txt); the other is `roofline_2`
+        try:   # the LM MLP block in one launch (B = 1), else the LM gate|up GEMV
+            roof_lm = measure_lm_ffn(model, B)
         except Exception as e:   # noqa: BLE001
-            print(f"bench: head roofline not measured: {e}", file=sys.stderr, flush=True)
-            roof_head = {"error": str(e)[:200]}
-    roof_attn = None
-    try:
-        roof_attn = measure_lm_attn(model, B, ctx_avg)
-    except Exception as e:   # noqa: BLE001
-        print(f"bench: LM attention half roofline not measured: {e}", file=sys.stderr, flush=True)
-    for r in (roof_lm, roof_head, roof_attn):
-        if r and "error" not in r:
-            in_loop_average(r, B)
-    roofline, roofline_2 = pick_roofline(roof_lm, roof_head, roof_attn)
-    tp_coll = None
-    if T > 1:   # after the timed loop: the null-collective passes corrupt the session's state
-        tp_coll = measure_tp_collective(lm_pass_maker(model, sess), model.config.decoder_config.num_hidden_layers,
-                                        world, dev)
-        if model.tp_head:   # the sharded diffusion head's S x head_layers all-reduces per token
-            hl = model.config.diffusion_head_config.head_layers
-            hc = measure_tp_collective(head_pass_maker(model, sess), hl * S / 2, world, dev)
-            tp_coll["head"] = dict(diffusion_call_us=hc["lm_pass_us"],
-                                   diffusion_call_us_null_collective=hc["lm_pass_us_null_collective"],
-                                   allreduce_us_per_call=hc["allreduce_us_per_pass"],
-                                   allreduce_calls_per_call=int(hl * S), allreduce_share=hc["allreduce_share"],
-                                   note="RCCL all-reduce of the [2B, H] head state after each head layer's "
-                                        "row-parallel down_proj (sharded head, tp_head)")
+            print(f"bench: LM MLP block roofline not measured: {e}", file=sys.stderr, flush=True)
+            roof_lm = None
+        roof_lm = roof_lm or measure_gemv(model, B)
+        roof_head = None
+        if world == 1 or T == 1:
+            try:
+                roof_head = measure_head_layers(model, B)
+            except Exception as e:   # noqa: BLE001
+                print(f"bench: head roofline not measured: {e}", file=sys.stderr, flush=True)
+                roof_head = {"error": str(e)[:200]}
+        roof_attn = None
+        try:
+            roof_attn = measure_lm_attn(model, B, ctx_avg)
+        except Exception as e:   # noqa: BLE001
+            print(f"bench: LM attention half roofline not measured: {e}", file=sys.stderr, flush=True)
+        for r in (roof_lm, roof_head, roof_attn):
+            if r and "error" not in r:
+                in_loop_average(r, B)
+        roofline, roofline_2 = pick_roofline(roof_lm, roof_head, roof_attn)
+        if T > 1:   # after the timed loop: the null-collective passes corrupt the session's state
+            tp_coll = measure_tp_collective(lm_pass_maker(model, sess), model.config.decoder_config.num_hidden_layers,
+                                            world, dev)
+            if model.tp_head:   # the sharded diffusion head's S x head_layers all-reduces per token
+                hl = model.config.diffusion_head_config.head_layers
+                hc = measure_tp_collective(head_pass_maker(model, sess), hl * S / 2, world, dev)
+                tp_coll["head"] = dict(diffusion_call_us=hc["lm_pass_us"],
+                                       diffusion_call_us_null_collective=hc["lm_pass_us_null_collective"],
+                                       allreduce_us_per_call=hc["allreduce_us_per_pass"],
+                                       allreduce_calls_per_call=int(hl * S), allreduce_share=hc["allreduce_share"],
+                                       note="RCCL all-reduce of the [2B, H] head state after each head layer's "
+                                            "row-parallel down_proj (sharded head, tp_head)")
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # bounded CPU sample, N=1 only
-        cpu = cpu_baseline(model.config, args.cpu_tokens, S, args.model)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:   # bounded CPU sample, N=1 only
+            cpu = cpu_baseline(model.config, args.cpu_tokens, S, args.model)
 
     if rank == 0:
         line = {
@@ -795,14 +842,13 @@ def main():
                        "model": f"VibeVoice-{args.model}", "global_batch": B * replicas, "seq_len": L,
                        "diffusion_steps": S, "parallelism": f"dp{replicas} (independent replicas), tp{T}",
                        "context_start": ctx0, "context_end": ctx1},
-            "roofline": roofline,
-            "roofline_2": roofline_2,
             "step_roofline": dict(roof("whole loop iteration", f"B={B} S={S}", bpt * B, dt / K),
                                   alg_bytes_per_token=int(bpt), head_layout=wb["head_layout"],
                                   note="SURVEY.md §8d bytes, each weight role counted once in the layout the loop "
                                        "reads (bench.py weight_bytes); avg_us = ms_per_step"),
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update(roofline=roofline, roofline_2=roofline_2, cpu_baseline=cpu)
         if tp_coll is not None:
             line["tp_collective"] = tp_coll
         print(json.dumps(line), flush=True)
@@ -823,7 +869,7 @@ def plumbing(args, world, rank, dev):
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
     tps, audio_per_s = throughput(dt, args.batch, args.steps, replicas)
     tp_coll = None
-    if args.tp > 1:   # the field's plumbing: a "pass" of 1 ms, 0.25 ms of it the collective
+    if args.full and args.tp > 1:   # the field's plumbing: a "pass" of 1 ms, 0.25 ms of it the collective
         tp_coll = measure_tp_collective(lambda null: (lambda: time.sleep(0.75e-3 if null else 1e-3)), 2, world,
                                         dev, iters=10)
     if rank == 0:

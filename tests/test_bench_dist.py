@@ -76,8 +76,9 @@ def test_bench_gpus_flag_launches_ranks():
 
 
 def test_bench_tp_groups_are_replicas():
-    """--gpus 4 --tp 2: two TP groups of consecutive ranks = 2 replicas."""
-    rc, line, err = _run_bench(["--gpus", "4", "--tp", "2", "--plumbing", "--steps", "5"])
+    """--gpus 4 --tp 2: two TP groups of consecutive ranks = 2 replicas
+    (--full: the collective share is one of the measurements behind it)."""
+    rc, line, err = _run_bench(["--gpus", "4", "--tp", "2", "--plumbing", "--full", "--steps", "5"])
     assert rc == 0, err[-2000:]
     assert line["n_gpus"] == 4 and line["config"]["parallelism"] == "dp2, tp2"
     # the collective-share field --tp adds (plumbing pass: 1 ms, 0.75 ms without the "collective")
