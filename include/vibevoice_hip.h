@@ -83,6 +83,14 @@ void vv_destroy(vv_ctx* ctx);
 int vv_bind_weight(vv_ctx* ctx, const char* name, const void* dev_ptr, const int64_t* shape, int ndim);
 /* Check every required weight is bound; allocate KV / codec state / workspaces. */
 int vv_finalize(vv_ctx* ctx);
+/* FP8 (OCP e4m3fn) weight-only storage of the LM projections is signalled by
+ * which weights are bound: each of lm.<l>.qkv_w / o_w / gu_w / down_w is bound
+ * either as the bf16 tensor under that name, or as the pair <name>8 (codes
+ * [N, K], weights.py:mfma_pack8 order) + <name>e (int8 [N], row scale 2^e);
+ * vv_finalize names the tensor when neither or half a pair is bound.  Returns 1
+ * when ctx holds quantised LM weights (the one-launch LM kernels are then off),
+ * else 0. */
+int vv_weights_quantized(vv_ctx* ctx);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

@@ -40,6 +40,27 @@ int vv_gemm_bf16(int M, int N, int K, const void* A, int64_t lda, const void* W,
  * producer of the loop's GEMMs (no bias / residual epilogues). */
 int vv_gemm_bf16_norm(int M, int N, int K, const void* A, int64_t lda, const void* norm_w, float eps, const void* W,
                       int epi, void* Y, int64_t ldy, vv_ctx* ws_ctx, vv_stream st);
+/* vv_gemm_bf16 / vv_gemm_bf16_norm on FP8 weight-only storage: `codes` is the
+ * [N, K] e4m3fn matrix in the byte order of weights.py:mfma_pack8
+ * (csrc/gemv_w8.hip), `exps` one int8 exponent per output row (scale 2^e).
+ * xf: 0 = A as is, 1 = A RMS-normalised on load (norm_w may be NULL).  epi as
+ * vv_gemm_bf16 (bias, res optional).  M <= 16 rows run the FP8 GEMV, more rows
+ * (or vv_gemv_w8(0)) dequantise the matrix and run the bf16 kernels. */
+int vv_gemm_w8(int M, int N, int K, const void* A, int64_t lda, const void* codes, const void* exps, int xf,
+               const void* norm_w, float eps, const void* bias, int epi, void* Y, int64_t ldy, const void* res,
+               vv_ctx* ws_ctx, vv_stream st);
+/* Test / A-B switch: 1 (default) = quantised GEMMs of <= 16 rows run the FP8
+ * GEMV (gemv_w8.hip); 0 = every quantised GEMM dequantises its matrix into the
+ * scratch and runs the bf16 kernels (bit for bit a bf16 engine on the
+ * dequantised weights). */
+int vv_gemv_w8(int on);
+/* Test hook: after a vv_lm_forward of ntok rows on ctx (synchronises the
+ * device): the q rows the last layer's q|k|v epilogue wrote ([ntok][n_heads x
+ * 128], RoPE applied) and the K / V cache entries of `layer` at (slots[i],
+ * pos[i]) for each row ([ntok][n_kv_heads][128] each; host slots / pos, device
+ * outputs).  ntok must be the row count of that pass. */
+int vv_diag_lm_qkv(vv_ctx* ctx, int ntok, int layer, const int* slots, const int* pos, void* q_out, void* k_out,
+                   void* v_out);
 /* GQA attention of nq query rows (q [nq, nh*128] bf16, RoPE applied) over a
  * caller-owned cache in the engine layout ([slot][kv_head][ctx][128], strides
  * in elements): row i attends keys [0, pos[i]] of slot slots[i] -> out

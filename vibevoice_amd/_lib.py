@@ -118,6 +118,10 @@ EXPORTS = [
     ("vv_persist_decision", I, [I, I, I, I, I, I]),
     ("vv_persistent_active", I, [P]),
     ("vv_norm_pack", I, [I]),
+    ("vv_weights_quantized", I, [P]),
+    ("vv_gemm_w8", I, [I, I, I, P, I64, P, P, I, P, F, P, I, P, I64, P, P, P]),
+    ("vv_gemv_w8", I, [I]),
+    ("vv_diag_lm_qkv", I, [P, I, I, ctypes.POINTER(I), ctypes.POINTER(I), P, P, P]),
 ]
 
 EPI = {"store": 0, "gelu": 1, "silu_mul": 2, "res": 3, "f32": 4}

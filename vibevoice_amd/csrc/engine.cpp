@@ -207,6 +207,10 @@ struct vv_ctx {
   bool hl_registered = false;   // counted in g_hl_ctxs (its device's grid-waiting contexts)
   bool head_gemv = true;        // the head FFN's GEMV layout is bound (head.<l>.gu_w / down_w)
   DevBuf rope_tab;   // [max_ctx][cos 64 | sin 64] bf16 (k_rope_table)
+  // FP8 weight-only LM projections (gemv_w8.hip): bound as <name>8 (e4m3 codes,
+  // mfma_pack8 order) + <name>e (int8 row exponents) instead of the bf16 <name>
+  bool quantized = false;
+  DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
 };
 
 // ------------------------------------------------------------------ helpers
@@ -229,6 +233,37 @@ static int need(vv_ctx* c, const std::string& n, const std::vector<int64_t>& sha
   return 0;
 }
 
+// An LM projection's weight operand: the bf16 matrix, or the FP8 codes + row exponents
+struct LmW {
+  const bf16* w = nullptr;
+  const unsigned char* w8 = nullptr;
+  const signed char* w8e = nullptr;
+};
+static LmW lm_w(vv_ctx* c, const std::string& n) {
+  LmW r;
+  r.w = W(c, n);
+  if (!r.w) {
+    r.w8 = (const unsigned char*)W(c, n + "8");
+    r.w8e = (const signed char*)W(c, n + "e");
+  }
+  return r;
+}
+// vv_finalize: the projection is bound either as bf16 `n` [N][K] or as the pair `n`8 [N][K] + `n`e [N]
+static int need_lm_w(vv_ctx* c, const std::string& n, int64_t N, int64_t K) {
+  const bool b = c->w.count(n) > 0, q = c->w.count(n + "8") > 0, e = c->w.count(n + "e") > 0;
+  if (b && (q || e)) FAIL("weight " + n + " is bound both as bf16 and as FP8 (" + n + "8 / " + n + "e)");
+  if (b) return need(c, n, {N, K});
+  if (!q && !e) FAIL("missing weight: " + n + " (bf16), or its FP8 pair " + n + "8 (codes) + " + n + "e (exponents)");
+  if (!q) FAIL("missing weight: " + n + "8 (FP8 codes; only the exponents " + n + "e are bound)");
+  if (!e) FAIL("missing weight: " + n + "e (FP8 row exponents; only the codes " + n + "8 are bound)");
+  if (K % 64) FAIL("FP8 weight " + n + "8: K = " + std::to_string(K) + " is not a multiple of 64");
+  if (c->tp_size > 1 || c->comm) FAIL("FP8 weights (" + n + "8) are not supported on a tensor-parallel engine");
+  CHK(need(c, n + "8", {N, K}));
+  CHK(need(c, n + "e", {N}));
+  c->quantized = true;
+  return 0;
+}
+
 static GemmArgs gemm_args(vv_ctx* c, int M, int N, int K, RowMap a, const bf16* w, int epi, RowMap out,
                           const bf16* bias = nullptr) {
   GemmArgs g;
@@ -245,6 +280,14 @@ static GemmArgs gemm_args(vv_ctx* c, int M, int N, int K, RowMap a, const bf16* 
   g.epi.out = out;
   g.ws = (float*)c->splitk_ws.p;
   g.counters = (unsigned*)c->splitk_cnt.p;
+  return g;
+}
+static GemmArgs gemm_args(vv_ctx* c, int M, int N, int K, RowMap a, const LmW& w, int epi, RowMap out,
+                          const bf16* bias = nullptr) {
+  GemmArgs g = gemm_args(c, M, N, K, a, w.w, epi, out, bias);
+  g.w8 = w.w8;
+  g.w8e = w.w8e;
+  g.w8_scratch = (bf16*)c->w8_scratch.p;
   return g;
 }
 
@@ -276,7 +319,7 @@ extern "C" int vv_norm_pack(int on) {
 }
 
 static int gemm(vv_ctx* c, GemmArgs g, hipStream_t st) {
-  if (!g.w) FAIL("gemm: null weight");
+  if (!g.w && !g.w8) FAIL("gemm: null weight");
   if (g.xf.kind == XF_NORM && g.M > 16) {
     // more rows than one MFMA tile: the GEMV / GEMM kernels would re-normalise
     // the A block in every workgroup (B = 32: LM gate|up 334 us); normalise it
@@ -928,7 +971,7 @@ void vv_destroy(vv_ctx* c) {
   DevBuf* bufs[] = {&c->norm_ws, &c->kv_k, &c->kv_v, &c->lm_ws, &c->attn_part, &c->attn_cnt, &c->valid_ids, &c->splitk_ws, &c->splitk_cnt,
                     &c->temb, &c->tfreq_tmp, &c->head_ws, &c->codec_ws, &c->slot_scratch, &c->unit_sb,
                     &c->rope_tab, &c->zero_rows, &c->hf_sync, &c->cs_sync, &c->m16_buf, &c->lf_sync,
-                    &c->cw_sync, &c->cw_slab, &c->cw_xbuf, &c->lf_slab, &c->la_part};
+                    &c->cw_sync, &c->cw_slab, &c->cw_xbuf, &c->lf_slab, &c->la_part, &c->w8_scratch};
   for (DevBuf* b : bufs) b->release();
   ConvNet* nets[] = {&c->dec, &c->sem, &c->aenc, &c->senc};
   for (ConvNet* n : nets) {
@@ -970,12 +1013,18 @@ int vv_finalize(vv_ctx* c) {
   for (int l = 0; l < k.n_layers; ++l) {
     const std::string p = "lm." + std::to_string(l);
     CHK(need(c, p + ".in_norm", {H}));
-    CHK(need(c, p + ".qkv_w", {c->qkv_n, H}));
+    CHK(need_lm_w(c, p + ".qkv_w", c->qkv_n, H));
     CHK(need(c, p + ".qkv_b", {c->qkv_n}));
-    CHK(need(c, p + ".o_w", {H, (int64_t)k.n_heads * d}));
+    CHK(need_lm_w(c, p + ".o_w", H, (int64_t)k.n_heads * d));
     CHK(need(c, p + ".post_norm", {H}));
-    CHK(need(c, p + ".gu_w", {2LL * k.intermediate, H}));
-    CHK(need(c, p + ".down_w", {H, k.intermediate}));
+    CHK(need_lm_w(c, p + ".gu_w", 2LL * k.intermediate, H));
+    CHK(need_lm_w(c, p + ".down_w", H, k.intermediate));
+  }
+  if (c->quantized) {
+    // the fallback's scratch (launch_gemm: more than 16 rows, forms k_gemv_w8 does not
+    // serve): sized once to the largest quantised matrix, never grown in a hot call
+    const size_t nk = std::max({(size_t)c->qkv_n * H, (size_t)H * k.n_heads * d, 2 * (size_t)k.intermediate * H});
+    CHK(c->w8_scratch.ensure(nk * sizeof(bf16)));
   }
   // ---- diffusion head
   const int L = k.head_layers, F = k.head_ffn, D = k.latent_dim;
@@ -1327,7 +1376,7 @@ extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launche
 }
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  return g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
+  return g_lm_attn && !c->quantized && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, LA_MAX_KEYS) &&
          lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
@@ -1350,7 +1399,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   const std::string p = "lm." + std::to_string(l);
   {
     // input_layernorm -> q|k|v projection (+bias) -> RoPE -> q / KV cache, one launch
-    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, W(c, p + ".qkv_w"), EPI_ROPE, RowMap{},
+    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, lm_w(c, p + ".qkv_w"), EPI_ROPE, RowMap{},
                            W(c, p + ".qkv_b"));
     g.xf = xf_norm(W(c, p + ".in_norm"), k.rms_eps);
     g.rope.nh = k.n_heads;
@@ -1411,7 +1460,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     at.part_ml2 = at.part_o2 + (size_t)P.ntok * k.n_heads * P.ngroups * d;
   }
   KCHK(launch_attn(at, st));
-  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), W(c, p + ".o_w"), EPI_RES, P.hm);
+  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), lm_w(c, p + ".o_w"), EPI_RES, P.hm);
   if (P.defer) {
     g.xf.kind = XF_ATTN_MERGE;
     g.xf.part_o = at.part_o;
@@ -1448,7 +1497,7 @@ static bool lm_ffn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
   const bool shape = P.ntok <= 2 ? lm_ffn_fits(k.hidden, k.intermediate, P.ntok)
                                  : (g_lm_ffn & 2) == 0 && c->lf_slab.p && lm_ffn16_fits(k.hidden, k.intermediate, P.ntok);
-  return g_lm_ffn && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
+  return g_lm_ffn && !c->quantized && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && shape && persist_on(c);
 }
 extern "C" int vv_lm_ffn_active(vv_ctx* c, int ntok) {
@@ -1484,9 +1533,9 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     return 0;
   }
   // post_attention_layernorm fused into gate|up's A load
-  GemmArgs g = gemm_args(c, P.ntok, 2 * I, H, P.hm, W(c, p + ".gu_w"), EPI_SILU_MUL, rowmap(P.act, I));
+  GemmArgs g = gemm_args(c, P.ntok, 2 * I, H, P.hm, lm_w(c, p + ".gu_w"), EPI_SILU_MUL, rowmap(P.act, I));
   g.xf = xf_norm(W(c, p + ".post_norm"), k.rms_eps);
-  GemmArgs d = gemm_args(c, P.ntok, H, I, rowmap(P.act, I), W(c, p + ".down_w"), EPI_RES, P.hm);
+  GemmArgs d = gemm_args(c, P.ntok, H, I, rowmap(P.act, I), lm_w(c, p + ".down_w"), EPI_RES, P.hm);
   tp_residual(c, d, P.hm);
   // prefill: SiLU*up written MFMA-fragment-packed for the down projection when
   // both take the 256 x 256 tile (16K rows: down 449 -> 388 us)
@@ -1901,7 +1950,7 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
   }
   if (!c->head_gemv)
     FAIL("diffusion head: " + std::to_string(h.R) + " rows need the GEMV layout (head.<l>.gu_w / down_w), which this "
-         "engine did not bind (packed for max_batch <= 2: weights.head_layout_for)");
+         "engine did not bind");
   CHK(head_gemm(c, h, g, st));
   g = gemm_args(c, h.R, H, F, rowmap(h.act, F), W(c, p + ".down_w"), EPI_RES, h.xh_m);
   g.epi.res = partial ? rowmap(c->zero_rows.p, H) : h.xh_m;
@@ -2332,6 +2381,88 @@ int vv_gemm_bf16_norm(int M, int N, int K, const void* A, int64_t lda, const voi
   KCHK(launch_gemm(g, (hipStream_t)vst));
   return 0;
 }
+
+// vv_gemm_bf16 / vv_gemm_bf16_norm on FP8 weight-only storage: codes [N][K] in
+// mfma_pack8 order + int8 row exponents; xf 0 = none, 1 = RMSNorm of the A rows
+// (norm_w optional); a quantised GemmArgs as the engine builds it (k_gemv_w8, or
+// the dequantise-and-bf16 fallback into the context's / a process-wide scratch)
+int vv_gemm_w8(int M, int N, int K, const void* A, int64_t lda, const void* codes, const void* exps, int xf,
+               const void* norm_w, float eps, const void* bias, int epi, void* Y, int64_t ldy, const void* res,
+               vv_ctx* c, vv_stream vst) {
+  if (!codes || !exps) FAIL("vv_gemm_w8: null codes / exponents");
+  if (xf != XF_NONE && xf != XF_NORM) FAIL("vv_gemm_w8: xf must be 0 (none) or 1 (RMSNorm)");
+  if (K % 64 || N % 16) FAIL("vv_gemm_w8: needs K % 64 == 0 and N % 16 == 0");
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.ksplit = 1;
+  g.a = rowmap(A, lda);
+  g.ldw = K;
+  g.w8 = (const unsigned char*)codes;
+  g.w8e = (const signed char*)exps;
+  g.epi.kind = epi;
+  g.epi.bias = (const bf16*)bias;
+  g.epi.out = rowmap(Y, ldy);
+  g.epi.res = rowmap(res, ldy);
+  if (xf == XF_NORM) g.xf = xf_norm((const bf16*)norm_w, eps);
+  static DevBuf ws, cnt, scratch;   // standalone calls (tests): process-wide workspaces
+  if (c) {
+    g.ws = (float*)c->splitk_ws.p;
+    g.counters = (unsigned*)c->splitk_cnt.p;
+  } else {
+    if (!cnt.p) {
+      CHK(ws.ensure(64ull << 20));
+      CHK(cnt.ensure(65536 * sizeof(unsigned)));
+      HIPCHK(hipMemset(cnt.p, 0, 65536 * sizeof(unsigned)));
+    }
+    g.ws = (float*)ws.p;
+    g.counters = (unsigned*)cnt.p;
+  }
+  if (c && c->w8_scratch.bytes >= (size_t)N * K * sizeof(bf16)) {
+    g.w8_scratch = (bf16*)c->w8_scratch.p;
+  } else if (!gemv_w8_serves(g)) {
+    CHK(scratch.ensure((size_t)N * K * sizeof(bf16)));
+    g.w8_scratch = (bf16*)scratch.p;
+  }
+  if (c) {
+    CHK(gemm(c, g, (hipStream_t)vst));
+    return 0;
+  }
+  KCHK(launch_gemm(g, (hipStream_t)vst));
+  return 0;
+}
+
+// Test hook: after a vv_lm_forward of ntok rows (synchronises the device), the q rows of
+// the last layer that ran ([ntok][n_heads * 128], RoPE applied) and, for row i, the K / V
+// cache entries of `layer` at (slots[i], pos[i]) ([ntok][n_kv_heads][128] each)
+int vv_diag_lm_qkv(vv_ctx* c, int ntok, int layer, const int* slots, const int* pos, void* q_out, void* k_out,
+                   void* v_out) {
+  if (!c || !c->finalized || !slots || !pos || !q_out || !k_out || !v_out) FAIL("vv_diag_lm_qkv: bad arguments");
+  const vv_config& k = c->cfg;
+  if (ntok < 1 || (size_t)ntok > c->lm_ws_tokens) FAIL("vv_diag_lm_qkv: no such pass");
+  if (layer < 0 || layer >= k.n_layers) FAIL("vv_diag_lm_qkv: bad layer");
+  HIPCHK(hipDeviceSynchronize());
+  const int H = k.hidden, d = k.head_dim, nhd = k.n_heads * d;
+  const bf16* q = (const bf16*)c->lm_ws.p + (size_t)ntok * (2 * (size_t)H + c->qkv_n);
+  HIPCHK(hipMemcpy(q_out, q, (size_t)ntok * nhd * sizeof(bf16), hipMemcpyDeviceToDevice));
+  for (int i = 0; i < ntok; ++i) {
+    if (slots[i] < 0 || slots[i] >= c->lm_slots || pos[i] < 0 || pos[i] >= c->kv.max_ctx) FAIL("vv_diag_lm_qkv: bad slot / position");
+    for (int h = 0; h < k.n_kv_heads; ++h) {
+      const long long base = (long long)layer * c->kv.s_layer + (long long)slots[i] * c->kv.s_slot + (long long)h * c->kv.s_head;
+      bf16* ko = (bf16*)k_out + ((size_t)i * k.n_kv_heads + h) * d;
+      bf16* vo = (bf16*)v_out + ((size_t)i * k.n_kv_heads + h) * d;
+      HIPCHK(hipMemcpy(ko, c->kv.k + base + (long long)pos[i] * d, d * sizeof(bf16), hipMemcpyDeviceToDevice));
+      // V: blocks of 32 positions, [dim][position] (common.h v_off): dim i at stride 32 elements
+      const long long v0 = base + (long long)(pos[i] >> 5) * (128 * 32) + (pos[i] & 31);
+      HIPCHK(hipMemcpy2D(vo, sizeof(bf16), c->kv.v + v0, 32 * sizeof(bf16), sizeof(bf16), d, hipMemcpyDeviceToDevice));
+    }
+  }
+  return 0;
+}
+
+int vv_weights_quantized(vv_ctx* c) { return c && c->finalized && c->quantized ? 1 : 0; }
 
 int vv_attention_bf16(int nq, int nh, int nkv, const void* q, const void* k_cache, const void* v_cache,
                       int64_t s_slot, int64_t s_head, const int* slots, const int* pos, int max_pos_p1, void* out,

@@ -1818,6 +1818,13 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
   if (a.xf.kind == XF_NORM && a.K % 8 != 0) return 1;
   if (a.epi.kind == EPI_ROPE && (a.rope.kv.d != 128 || !a.rope.pos || !a.rope.slots)) return 1;
   if (a.epi.kind == EPI_CFG_DPM && (a.M > 16 || 2 * a.dpm.n != a.M)) return 1;
+  if (a.w8) {   // FP8 weight-only storage: its own GEMV, or dequantise this matrix and go on in bf16
+    if (gemv_w8_serves(a)) return launch_gemv_w8(a, st);
+    if (!a.w8e || !a.w8_scratch || a.K % 64) return 1;
+    if (int rc = launch_dequant_w8(a.w8, a.w8e, a.w8_scratch, a.N, a.K, st)) return rc;
+    a.w = a.w8_scratch;
+    a.w8 = nullptr;
+  }
   a.stamps = g_stamps;
   if (g_shape_log) {   // VV_GEMM_LOG=1: one line per launch (shape census for profiles/)
     fprintf(stderr, "vv_gemm M=%d N=%d K=%d xf=%d epi=%d\n", a.M, a.N, a.K, a.xf.kind, a.epi.kind);

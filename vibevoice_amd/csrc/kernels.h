@@ -81,6 +81,13 @@ struct GemmArgs {
   unsigned long long* stamps;  // diagnostic builds only: 4 s_memrealtime stamps per workgroup
   int keep;               // weights re-read soon (diffusion head): default cache policy, not nt
   int apack;              // k_gemm_xl: A rows in MFMA-fragment order (blocks (row tile, chunk) of 1 KB, as W)
+  // FP8 weight-only storage (gemv_w8.hip): w8 != nullptr replaces w by e4m3 codes in
+  // mfma_pack8 order + one int8 exponent per output row (scale 2^e).  launch_gemm runs
+  // k_gemv_w8 where it serves the form, else dequantises into w8_scratch (bf16 [N][K],
+  // mfma_pack order) and runs the bf16 launch on it
+  const unsigned char* w8;
+  const signed char* w8e;
+  bf16* w8_scratch;
 };
 
 struct NormArgs {
@@ -401,6 +408,12 @@ void codec_wide_oversubscribe(int on);
 
 size_t gemv_mix_lds(int M, int T, int C);
 int launch_gemm(GemmArgs a, hipStream_t st);
+// gemv_w8.hip: true when k_gemv_w8 runs this quantised GemmArgs (M <= 16, XF_NONE / XF_NORM
+// without adaLN, the epi_tile epilogues) and the kernel path is switched on (vv_gemv_w8)
+bool gemv_w8_serves(const GemmArgs& a);
+int launch_gemv_w8(const GemmArgs& a, hipStream_t st);
+// codes [N][K] (mfma_pack8) x 2^ex[n] -> out bf16 [N][K] (mfma_pack), exact
+int launch_dequant_w8(const unsigned char* codes, const signed char* ex, bf16* out, int N, int K, hipStream_t st);
 int launch_sum_rows(SumRows s, long long count, hipStream_t st);
 int launch_rmsnorm(NormArgs a, hipStream_t st);
 int launch_dwconv(DwArgs a, hipStream_t st);

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import codec_channels, head_tp_check, pack
+from .weights import W8_CODES, check_weight_dtype, codec_channels, head_tp_check, pack
 
 _VALID_IDS_DEFAULT = None
 
@@ -60,12 +60,23 @@ def engine_config(cfg: VibeVoiceConfig, max_batch, max_ctx, tp_size=1, tp_head=F
     return c
 
 
+def normalize_persistent(persistent):
+    """Engine's `persistent` option: True / 1 -> True (on), False / 0 -> False
+    (off), "follow" -> "follow"; anything else raises ValueError."""
+    if isinstance(persistent, str):
+        if persistent == "follow":
+            return "follow"
+    elif isinstance(persistent, (bool, int)) and persistent in (0, 1):
+        return bool(persistent)
+    raise ValueError(f"persistent={persistent!r}: expected True / 1 (on), False / 0 (off) or \"follow\"")
+
+
 class Engine:
     """One device-resident VibeVoice model instance."""
 
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
-                 persistent=True):
+                 persistent=True, weight_dtype=None):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -78,7 +89,12 @@ class Engine:
         kernels (vv_set_persistent 0); "follow" runs them while exactly one
         context of the device is registered, without registering itself (the
         standalone tokenizer API's codec context: it computes with its owner's
-        kernels and never demotes it)."""
+        kernels and never demotes it).
+        weight_dtype: None = bf16 weights; "fp8_e4m3" = the LM projections as
+        OCP e4m3 codes + a power-of-two scale per row (weights.pack; tp_size 1
+        only).  With `packed`, the format is the one those weights were packed in."""
+        persistent = normalize_persistent(persistent)
+        check_weight_dtype(weight_dtype, tp_size)
         L = _lib.lib()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -95,7 +111,11 @@ class Engine:
             head_tp_check(cfg, tp_size)
         with torch.cuda.device(self.device):
             self.w = packed if packed is not None else pack(state_dict, cfg, self.device, tp_rank=tp_rank,
-                                                            tp_size=tp_size, tp_head=self.tp_head)
+                                                            tp_size=tp_size, tp_head=self.tp_head,
+                                                            weight_dtype=weight_dtype)
+            if packed is not None:
+                weight_dtype = "fp8_e4m3" if any(k.endswith("_w" + W8_CODES) for k in packed) else None
+            self.weight_dtype = weight_dtype
             h = ctypes.c_void_p()
             self._ecfg = engine_config(cfg, max_batch, max_ctx, tp_size, self.tp_head)
             _lib.check(L.vv_create(ctypes.byref(self._ecfg), self.device.index or 0, ctypes.byref(h)), "create")
@@ -150,6 +170,9 @@ class Engine:
         """Zero every grid-wait counter of this context (vv_sync_reset; after a
         wait gave up).  Synchronises the device."""
         _lib.check(_lib.lib().vv_sync_reset(self.h), "sync_reset")
+
+    def weights_quantized(self):
+        return _lib.lib().vv_weights_quantized(self.h) == 1
 
     def persistent_active(self):
         return _lib.lib().vv_persistent_active(self.h) == 1

@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .engine import Engine
-from .weights import head_tp_default, synthetic_state_dict
+from .weights import check_weight_dtype, head_tp_default, synthetic_state_dict
 
 
 @dataclass
@@ -173,7 +173,7 @@ class VibeVoiceTokenConstraintProcessor:
 
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VibeVoiceConfig, state_dict, device="cuda", attn_implementation="hip",
-                 max_batch=8, max_ctx=8192, tp_group=None, tp_head=None, persistent=True):
+                 max_batch=8, max_ctx=8192, tp_group=None, tp_head=None, persistent=True, weight_dtype=None):
         """tp_group: a torch.distributed process group whose ranks (one per GPU)
         tensor-parallel-shard the Qwen2 backbone over RCCL; every
         rank then runs generate() on the same inputs (SPMD) and gets the same
@@ -181,7 +181,13 @@ class VibeVoiceForConditionalGenerationInference:
         diffusion head's FFN over the group too (None: when its per-step
         weights exceed the Infinity Cache, i.e. VibeVoice-Large).  persistent:
         False keeps the engine off the grid-waiting one-launch kernels
-        (vv_set_persistent; for a GPU shared by several processes)."""
+        (vv_set_persistent; for a GPU shared by several processes).
+        weight_dtype: None = bf16 weights (the default); "fp8_e4m3" = the LM
+        projections quantised at load time to OCP e4m3 with a power-of-two
+        scale per output row (INTEGRATION.md §2 "Weight formats"); any other
+        value, or FP8 with a tensor-parallel group, raises ValueError."""
+        check_weight_dtype(weight_dtype)
+        self.weight_dtype = weight_dtype
         self.config = config
         self.attn_implementation = attn_implementation
         self.device = torch.device(device)
@@ -191,6 +197,7 @@ class VibeVoiceForConditionalGenerationInference:
         if tp_group is not None:
             import torch.distributed as dist
             tp_rank, tp_size = dist.get_rank(tp_group), dist.get_world_size(tp_group)
+            check_weight_dtype(weight_dtype, tp_size)
             if tp_size > 1:
                 box = [Engine.tp_unique_id() if tp_rank == 0 else None]
                 dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
@@ -199,7 +206,8 @@ class VibeVoiceForConditionalGenerationInference:
         self.tp_head = head_tp_default(config, tp_size) if tp_head is None else bool(tp_head and tp_size > 1)
         self.engine = Engine(config, state_dict, self.device, max_batch=max_batch, tp_head=self.tp_head,
                              max_ctx=min(max_ctx, config.decoder_config.max_position_embeddings),
-                             tp_rank=tp_rank, tp_size=tp_size, tp_unique_id=uid, persistent=persistent)
+                             tp_rank=tp_rank, tp_size=tp_size, tp_unique_id=uid, persistent=persistent,
+                             **({} if weight_dtype is None else {"weight_dtype": weight_dtype}))
         self.ddpm_inference_steps = config.diffusion_head_config.ddpm_num_inference_steps
         self.model = _ModelView(self)
         self.use_graphs = True          # capture the steady-state loop body into hipGraphs
@@ -247,7 +255,7 @@ class VibeVoiceForConditionalGenerationInference:
 
     @classmethod
     def from_pretrained(cls, path, torch_dtype=torch.bfloat16, device_map="cuda", attn_implementation="hip",
-                        synthetic_seed=0, **kw):
+                        synthetic_seed=0, weight_dtype=None, **kw):
         """`path`: a checkpoint dir (config.json + *.safetensors), or
         "synthetic:1.5B" / "synthetic:Large" for seeded random weights at the
         real shapes (no checkpoints are reachable offline).
@@ -255,7 +263,11 @@ class VibeVoiceForConditionalGenerationInference:
         `device_map` / `torch_dtype` as the demos pass them
         (demo/inference_from_file.py:282-305): a CUDA (ROCm) device and bf16.
         The CPU / MPS / fp32 branches of the demo are refused with an explicit
-        error — there is no CPU path behind this class."""
+        error — there is no CPU path behind this class.
+
+        `weight_dtype`: None (bf16) or "fp8_e4m3": the LM projections are
+        quantised from the bf16 checkpoint while loading (no FP8 on-disk format)."""
+        check_weight_dtype(weight_dtype)
         resolve_dtype(torch_dtype)
         dev = resolve_device(device_map)
         if str(path).startswith("synthetic:"):
@@ -264,7 +276,7 @@ class VibeVoiceForConditionalGenerationInference:
         else:
             cfg = VibeVoiceConfig.from_json_file(os.path.join(path, "config.json"))
             sd = load_state_dict(path, cfg)
-        return cls(cfg, sd, dev, attn_implementation=attn_implementation, **kw)
+        return cls(cfg, sd, dev, attn_implementation=attn_implementation, weight_dtype=weight_dtype, **kw)
 
     @classmethod
     def _from_config(cls, config, torch_dtype=None, device_map="cuda", attn_implementation="hip", seed=0, **kw):

@@ -203,6 +203,79 @@ def mfma_unpack(w):
     return w.reshape(N // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).contiguous().reshape(N, K)
 
 
+# ------------------------------------------------------------------ FP8 weight-only storage
+WEIGHT_DTYPES = (None, "fp8_e4m3")
+# an LM projection quantised under engine name n is stored as n + "8" (codes) and n + "e" (exponents)
+W8_CODES, W8_EXPS = "8", "e"
+LM_QUANTIZED = ("qkv_w", "o_w", "gu_w", "down_w")
+_E_MIN = -100   # exponent clamp: 2^-100 x the smallest e4m3 subnormal (2^-9) is still a normal bf16
+
+
+def check_weight_dtype(weight_dtype, tp_size=1):
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype={weight_dtype!r} is not supported; supported: {list(WEIGHT_DTYPES)}")
+    if weight_dtype is not None and tp_size > 1:
+        raise ValueError(f"weight_dtype={weight_dtype!r} is not supported with tensor parallelism "
+                         f"(tp_size={tp_size}); use bf16 weights or tp_size=1")
+    return weight_dtype
+
+
+def quantize_rows_e4m3(w):
+    """[N, K] -> (codes [N, K] torch.float8_e4m3fn (OCP), e [N] int8) with
+    w ~ codes * 2**e[n]: e[n] is the smallest integer with amax(row) / 2**e <= 448
+    (an all-zero row: e = 0), so no code saturates and the NaN codes never occur.
+    A power-of-two scale keeps the dequantised value exact in bf16."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    # amax = m * 2**x, m in [0.5, 1); 448 * 2**e = 0.875 * 2**(e + 9): exact, no division
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(_E_MIN, 127)
+    codes = torch.ldexp(wf, -e[:, None]).to(torch.float8_e4m3fn)
+    return codes, e.to(torch.int8)
+
+
+def dequantize_rows(codes, e):
+    """codes * 2**e[n] as bf16; exact (4 significant bits, a power-of-two scale)."""
+    return torch.ldexp(codes.float(), e.to(torch.int32)[:, None]).to(torch.bfloat16)
+
+
+def mfma_pack8(c):
+    """[N, K] one-byte codes -> the same shape in the FP8 GEMV's order
+    (csrc/gemv_w8.hip header): mfma_pack's tile and lane mapping with two
+    32-column chunks per block, so block (tile t, chunk pair p) of 16 rows x 64
+    columns is 1 KB contiguous and lane l holds 16 bytes:
+    W[16t + (l & 15)][64p + 8(l >> 4) .. +7] then W[..][64p + 32 + 8(l >> 4) .. +7]."""
+    N, K = c.shape
+    assert N % 16 == 0 and K % 64 == 0, (N, K)
+    b = c.view(torch.uint8)
+    b = b.reshape(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous().reshape(N, K)
+    return b.view(c.dtype)
+
+
+def mfma_unpack8(c):
+    N, K = c.shape
+    b = c.view(torch.uint8)
+    b = b.reshape(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous().reshape(N, K)
+    return b.view(c.dtype)
+
+
+def fake_quantize_state_dict(sd, cfg: VibeVoiceConfig):
+    """A copy of the reference-named state dict with exactly the tensors
+    pack(weight_dtype="fp8_e4m3") quantises replaced by their dequantised
+    values: q/k/v/o/gate/up/down of every LM layer.  The scales are per output
+    row and pack()'s re-packing only permutes rows, so quantising the reference
+    matrices row by row gives the same values as quantising the packed ones."""
+    out = dict(sd)
+    for i in range(cfg.decoder_config.num_hidden_layers):
+        p = f"{LM}layers.{i}."
+        for n in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
+                  "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"):
+            w = sd[p + n + ".weight"]
+            out[p + n + ".weight"] = dequantize_rows(*quantize_rows_e4m3(w)).to(w.dtype)
+    return out
+
+
 def is_gemm_weight(name):
     """Engine weights consumed by the MFMA GEMM / GEMV kernels (MFMA-packed)."""
     if not name.endswith("_w") or name.endswith(".dw_w"):
@@ -266,7 +339,8 @@ def head_tp_default(cfg: VibeVoiceConfig, tp_size):
     return tp_size > 1 and hc.head_layers * 3 * F * hc.hidden_size * 2 > (192 << 20)
 
 
-def pack(sd, cfg: VibeVoiceConfig, device, with_acoustic_encoder=True, tp_rank=0, tp_size=1, tp_head=False):
+def pack(sd, cfg: VibeVoiceConfig, device, with_acoustic_encoder=True, tp_rank=0, tp_size=1, tp_head=False,
+         weight_dtype=None):
     """Reference state dict -> {engine name: contiguous device tensor}.
 
     The diffusion head's FFN is packed once, in the GEMV layout (gate|up tiles of
@@ -280,8 +354,15 @@ def pack(sd, cfg: VibeVoiceConfig, device, with_acoustic_encoder=True, tp_rank=0
     lm_head, diffusion head, codec and connectors are replicated, except with
     tp_head: the diffusion head's FFN then splits the same way (gate|up rows of
     the rank's hidden columns, the matching down_proj input columns; SURVEY.md
-    §8e)."""
+    §8e).
+
+    weight_dtype="fp8_e4m3": the LM's q|k|v, o_proj, gate|up and down_proj are
+    stored as OCP e4m3 codes with one power-of-two scale per packed output row
+    (quantize_rows_e4m3, after the re-packing): `lm.<l>.qkv_w8` holds the codes
+    in mfma_pack8 order, `lm.<l>.qkv_we` the int8 exponents, and no bf16 copy is
+    kept.  Everything else stays bf16.  Not with tp_size > 1."""
     dt = torch.bfloat16
+    check_weight_dtype(weight_dtype, tp_size)
     tp_check(cfg, tp_size)
 
     def t(x):
@@ -312,6 +393,14 @@ def pack(sd, cfg: VibeVoiceConfig, device, with_acoustic_encoder=True, tp_rank=0
         out[e + "o_w"] = t(sd[p + "self_attn.o_proj.weight"][:, qs])
         out[e + "gu_w"] = t(_gu(sd[p + "mlp.gate_proj.weight"][fs], sd[p + "mlp.up_proj.weight"][fs]))
         out[e + "down_w"] = t(sd[p + "mlp.down_proj.weight"][:, fs])
+        if weight_dtype == "fp8_e4m3":
+            for n in LM_QUANTIZED:
+                w = out.pop(e + n)
+                if w.shape[1] % 64:
+                    raise ValueError(f"weight_dtype='fp8_e4m3' needs K % 64 == 0; {e + n} has K = {w.shape[1]}")
+                codes, ex = quantize_rows_e4m3(w)
+                out[e + n + W8_CODES] = mfma_pack8(codes)
+                out[e + n + W8_EXPS] = ex.contiguous()
 
     hc = cfg.diffusion_head_config
     out["head.noisy_w"] = t(sd[HEAD + "noisy_images_proj.weight"])
