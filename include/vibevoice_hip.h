@@ -91,6 +91,23 @@ int vv_finalize(vv_ctx* ctx);
  * when ctx holds quantised LM weights (the one-launch LM kernels are then off),
  * else 0. */
 int vv_weights_quantized(vv_ctx* ctx);
+/* KV cache format of the LM, per context: dtype 0 = bf16 (the default), 1 = FP8
+ * (OCP e4m3): K (after RoPE) and V stored as one-byte codes in the bf16 cache's
+ * geometry plus one int8 exponent per cached row (the 128 values of one layer,
+ * slot, kv head and position; value = code * 2^e, e the smallest integer with
+ * amax / 2^e <= 448) -- 129/256 of the bf16 cache's bytes.  Attention then reads
+ * the dequantised values for every key, the pass's own tokens included
+ * (csrc/kv_fp8.hip).  Callable after vv_create and before vv_finalize, which
+ * allocates the cache; later calls, other values and tensor-parallel engines
+ * are errors.  Under FP8 KV the one-launch LM attention kernel is off
+ * (vv_lm_attn_active reports 0).
+ *   vv_kv_dtype: the context's format (0 / 1)
+ *   vv_kv_bytes: *bytes = device bytes of the finalized context's KV cache,
+ *     exponents included, the append staging excluded (an error before
+ *     vv_finalize; status return like every entry point here) */
+int vv_set_kv_dtype(vv_ctx* ctx, int dtype);
+int vv_kv_dtype(vv_ctx* ctx);
+int vv_kv_bytes(vv_ctx* ctx, long long* bytes);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

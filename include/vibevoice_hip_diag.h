@@ -61,6 +61,21 @@ int vv_gemv_w8(int on);
  * outputs).  ntok must be the row count of that pass. */
 int vv_diag_lm_qkv(vv_ctx* ctx, int ntok, int layer, const int* slots, const int* pos, void* q_out, void* k_out,
                    void* v_out);
+/* Test hooks on the context's own KV cache, either format (synchronous; device
+ * buffers of bf16 rows [layer][kv_head][p1 - p0][128], K and V):
+ *   vv_diag_kv_read: positions [p0, p1) of `slot` as cached (dequantised under FP8 KV)
+ *   vv_diag_kv_write: store rows there (quantised under FP8 KV)
+ *   vv_diag_attn_ctx: only the attention launch of `layer`, no append: nq query
+ *     rows q [nq][n_heads x 128] (RoPE applied) at device tables slots / pos (row
+ *     i attends keys [0, pos[i]]) -> out [nq][n_heads x 128].  form: 0 = decode
+ *     kernel as planned (splits by vv_attn_tune; in-kernel merge or k_attn_merge),
+ *     1 = prefill kernel, 2 = decode with the deferred merge (2..8 splits), 3 =
+ *     decode with the grouped merge (groups of 2 splits); the partials of 2 and 3,
+ *     which o_proj merges in a pass, are merged by a diagnostic kernel. */
+int vv_diag_kv_read(vv_ctx* ctx, int slot, int p0, int p1, void* k_out, void* v_out);
+int vv_diag_kv_write(vv_ctx* ctx, int slot, int p0, int p1, const void* k_in, const void* v_in);
+int vv_diag_attn_ctx(vv_ctx* ctx, int layer, int nq, const void* q, const int* slots, const int* pos, int form,
+                     void* out, vv_stream st);
 /* GQA attention of nq query rows (q [nq, nh*128] bf16, RoPE applied) over a
  * caller-owned cache in the engine layout ([slot][kv_head][ctx][128], strides
  * in elements): row i attends keys [0, pos[i]] of slot slots[i] -> out

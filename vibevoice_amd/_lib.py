@@ -37,6 +37,9 @@ EXPORTS = [
     ("vv_bind_weight", I, [P, ctypes.c_char_p, P, ctypes.POINTER(I64), I]),
     ("vv_finalize", I, [P]),
     ("vv_set_valid_ids", I, [P, I, ctypes.POINTER(I)]),
+    ("vv_set_kv_dtype", I, [P, I]),
+    ("vv_kv_dtype", I, [P]),
+    ("vv_kv_bytes", I, [P, ctypes.POINTER(ctypes.c_longlong)]),
     ("vv_set_schedule", I, [P, I, ctypes.POINTER(F), P, P]),
     ("vv_lm_forward", I, [P, I, P, I, P, P, I, I, P, P, P, P]),
     ("vv_kv_copy", I, [P, I, P, P, P, P]),
@@ -122,6 +125,9 @@ EXPORTS = [
     ("vv_gemm_w8", I, [I, I, I, P, I64, P, P, I, P, F, P, I, P, I64, P, P, P]),
     ("vv_gemv_w8", I, [I]),
     ("vv_diag_lm_qkv", I, [P, I, I, ctypes.POINTER(I), ctypes.POINTER(I), P, P, P]),
+    ("vv_diag_kv_read", I, [P, I, I, I, P, P]),
+    ("vv_diag_kv_write", I, [P, I, I, I, P, P]),
+    ("vv_diag_attn_ctx", I, [P, I, I, P, P, P, I, P, P]),
 ]
 
 EPI = {"store": 0, "gelu": 1, "silu_mul": 2, "res": 3, "f32": 4}

@@ -90,8 +90,41 @@ DEV void astamp(const AttnArgs& a, int which) {
   }
 }
 
-template <int G, int NW>
+// ST = the cache's storage type: bf16, or unsigned char for the FP8 (e4m3) cache
+// (kernels.h KV8).  The FP8 form loads a fragment's 8 codes with one 8-byte load,
+// converts them to bf16 in registers (exact, cvt8) and runs the same MFMAs; the
+// rows' power-of-two scales go on the 16 x 16 score tile, not on the operands:
+// the fp32 scores of key column j times 2^eK[j] after Q.K^T, the fp32
+// probabilities of key j times 2^eV[j] before they are rounded to bf16 for P.V.
+// A power of two commutes with both roundings, so the result is bit for bit
+// that of the bf16 form over a cache holding the dequantised values.
+template <class ST>
+struct KvFrag {   // one lane's MFMA operand piece of 8 cached values, as loaded
+  typedef bf16x8 type;
+};
+template <>
+struct KvFrag<unsigned char> {
+  typedef u32x2 type;
+};
+template <class ST>
+DEV const ST* kv_k(const AttnArgs& a) {
+  if constexpr (std::is_same<ST, bf16>::value) return a.kv.k;
+  else return a.kv8.k;
+}
+template <class ST>
+DEV const ST* kv_v(const AttnArgs& a) {
+  if constexpr (std::is_same<ST, bf16>::value) return a.kv.v;
+  else return a.kv8.v;
+}
+DEV bf16x8 kv_bf(bf16x8 f) { return f; }
+DEV bf16x8 kv_bf(u32x2 f) { return cvt8(f[0], f[1]); }
+// byte i of a dword of int8 exponents
+DEV int exp_at(unsigned w, int i) { return (int)(signed char)(w >> (8 * i)); }
+
+template <int G, int NW, class ST = bf16>
 __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
+  constexpr bool F8 = !std::is_same<ST, bf16>::value;
+  typedef typename KvFrag<ST>::type frag;
   __shared__ float wm[NW][G], wl[NW][G];
   __shared__ float wo[NW][G][128];
   __shared__ __attribute__((aligned(16))) bf16 pt[NW][16][32];
@@ -142,8 +175,10 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   const int w1 = min(k1, w0 + per);
   const long long cbase = (long long)a.layer * a.kv.s_layer + (long long)slot * a.kv.s_slot +
                           (long long)kh * a.kv.s_head;
-  const bf16* K = a.kv.k + cbase;             // [ctx][128]
-  const bf16* VB = a.kv.v + cbase;            // 32-position blocks of [128][32] (v_off)
+  const ST* K = kv_k<ST>(a) + cbase;          // [ctx][128]
+  const ST* VB = kv_v<ST>(a) + cbase;         // 32-position blocks of [128][32] (v_off)
+  const signed char* EK = F8 ? a.kv8.ek + cbase / d : nullptr;   // [ctx] row exponents
+  const signed char* EV = F8 ? a.kv8.ev + cbase / d : nullptr;
   const bf16x8 z8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
 
   f32x4 o[8];
@@ -158,31 +193,34 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   // K / V fragments of two 32-key steps in flight per wave (two register sets,
   // both issued before the first step computes): a 512-key split (65K context)
   // is 64 keys per wave, so all of a workgroup's K / V is requested at once
-  bf16x8 kA[2][4], vA[8], kB[2][4], vB[8];
+  frag kA[2][4], vA[8], kB[2][4], vB[8];
+  // FP8: the exponents of a set's score columns, keys c0 + r and c0 + 16 + r (K in byte 0, V in byte 1)
+  int xA[2] = {0, 0}, xB[2] = {0, 0};
   // Loads are unconditional, from positions clamped into [0, w1): no branch
   // and no per-load wait.  (Guarded V loads followed by the tail mask compiled
   // to a branch + s_waitcnt vmcnt(0) after EACH of a step's 8 V loads -- eight
   // serialized memory round trips per step.)  Keys past w1 are masked where
   // their values are used: S to -inf (so P = 0) and V to 0 on the tail step
   // (the clamped rows hold other keys' values, and 0 x NaN would not vanish).
-  auto load = [&](int c0, bf16x8 (&kf)[2][4], bf16x8 (&vf)[8]) {
+  auto load = [&](int c0, frag (&kf)[2][4], frag (&vf)[8], int (&xf)[2]) {
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
       const int key = min(c0 + 16 * tt + r, w1 - 1);   // B operand of S: col = key
 #pragma unroll
-      for (int c = 0; c < 4; ++c) kf[tt][c] = *(const bf16x8*)(K + (long long)key * d + 32 * c + 8 * g);
+      for (int c = 0; c < 4; ++c) kf[tt][c] = *(const frag*)(K + (long long)key * d + 32 * c + 8 * g);
+      if constexpr (F8) xf[tt] = (EK[key] & 0xff) | (EV[key] << 8);
     }
     const int kb = min(c0 + 8 * g, (w1 - 1) & ~7);      // B operand of O: k = keys kb .. kb+7, col = dim
 #pragma unroll
-    for (int j = 0; j < 8; ++j) vf[j] = *(const bf16x8*)(VB + v_off(16 * j + r, kb));
+    for (int j = 0; j < 8; ++j) vf[j] = *(const frag*)(VB + v_off(16 * j + r, kb));
   };
-  if (w0 < w1) load(w0, kA, vA);
-  if (w0 + 32 < w1) load(w0 + 32, kB, vB);
+  if (w0 < w1) load(w0, kA, vA, xA);
+  if (w0 + 32 < w1) load(w0 + 32, kB, vB, xB);
   if (a.stamps) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     astamp(a, 1);
   }
-  auto step = [&](int c0, const bf16x8 (&kc)[2][4], bf16x8 (&vc)[8]) {   // vc is masked in place
+  auto step_bf = [&](int c0, const bf16x8 (&kc)[2][4], bf16x8 (&vc)[8], const int (&xc)[2]) {   // vc is masked in place
     if (c0 + 32 > w1) {   // the wave's tail step (uniform): keys kb + e >= w1 contribute nothing
       const int kb = c0 + 8 * g;
 #pragma unroll
@@ -201,6 +239,10 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
     float p[2][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      if constexpr (F8) {
+        sacc[0][i] = ldexpf(sacc[0][i], (int)(signed char)xc[0]);
+        sacc[1][i] = ldexpf(sacc[1][i], (int)(signed char)xc[1]);
+      }
       float s0 = c0 + r < w1 ? sacc[0][i] * a.scale : -INFINITY;
       float s1 = c0 + 16 + r < w1 ? sacc[1][i] * a.scale : -INFINITY;
       float mx = fmaxf(s0, s1);
@@ -220,19 +262,36 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) pt[wave][4 * g + i][16 * tt + r] = (bf16)p[tt][i];
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (F8) pt[wave][4 * g + i][16 * tt + r] = (bf16)ldexpf(p[tt][i], xc[tt] >> 8);
+        else pt[wave][4 * g + i][16 * tt + r] = (bf16)p[tt][i];
+      }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const bf16x8 pa = *(const bf16x8*)&pt[wave][r][8 * g];
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = amfma(pa, vc[j], o[j]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
+  auto step = [&](int c0, frag (&kq)[2][4], frag (&vq)[8], const int (&xc)[2]) {
+    if constexpr (F8) {   // codes -> bf16 in registers, then the bf16 step
+      bf16x8 kc[2][4], vc[8];
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) kc[tt][c] = kv_bf(kq[tt][c]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vc[j] = kv_bf(vq[j]);
+      step_bf(c0, kc, vc, xc);
+    } else {
+      step_bf(c0, kq, vq, xc);
+    }
+  };
   for (int c0 = w0; c0 < w1; c0 += 64) {
-    step(c0, kA, vA);
-    if (c0 + 64 < w1) load(c0 + 64, kA, vA);
+    step(c0, kA, vA, xA);
+    if (c0 + 64 < w1) load(c0 + 64, kA, vA, xA);
     if (c0 + 32 < w1) {
-      step(c0 + 32, kB, vB);
-      if (c0 + 96 < w1) load(c0 + 96, kB, vB);
+      step(c0 + 32, kB, vB, xB);
+      if (c0 + 96 < w1) load(c0 + 96, kB, vB, xB);
     }
   }
   // this wave's (m, l, O): lane holds O[head 4g+i][dim 16j + r]
@@ -577,7 +636,6 @@ int launch_final_head(int R, int H, const bf16* h, const int* idx, const bf16* n
 // [0, max position of its rows].
 constexpr int PF_Q = 32;
 constexpr float PF_LAZY = 8.f;       // running-max slack (log2 units) before O is rescaled
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // 32-key steps per LDS stage (one barrier and one vmcnt wait per stage)
 constexpr int PF_SUB = 2;
 constexpr int PF_STAGE = PF_SUB * 16 * 512;   // bf16 elements per stage: per step 8 K + 8 V fragment blocks
@@ -628,14 +686,28 @@ DEV void wait_vm(int n) {
 // with one wave and two with two (the per-step barrier waits for the loaded
 // ones), and 215 VGPRs allow no second workgroup; 12 waves of ~150 VGPRs fill
 // every SIMD with three.
-template <int G, int QW>
+// a lane's piece of a staged fragment block: bf16 lane-linear 16 bytes; FP8 [low dwords | high dwords]
+DEV bf16x8 pf_frag(const bf16* blk, int lane) { return *(const bf16x8*)(blk + lane * 8); }
+DEV bf16x8 pf_frag(const unsigned char* blk, int lane) {
+  return cvt8(*(const unsigned*)(blk + lane * 4), *(const unsigned*)(blk + 256 + lane * 4));
+}
+
+// ST as k_attn's.  The FP8 form stages a fragment block (64 lanes x 8 codes, 512
+// bytes) with two 4-byte global_load_lds per lane -- LDS-DMA has no 8-byte form --
+// so a block is [low dwords of the 64 lanes | high dwords] and a lane reads its
+// two dwords lane-linear; a stage's 2 x 64 exponent bytes ride the same ring
+// (one 4-byte DMA of the last wave: lanes 0-15 the keys' K exponents, 16-31 the V
+// exponents, into 256 bytes per stage behind the fragment stages), and a lane reads
+// its 8 keys' exponents from LDS.  The scales go on S^T and P^T as in k_attn.
+template <int G, int QW, class ST = bf16>
 __global__ void __launch_bounds__(64 * G * 2 / QW) __attribute__((amdgpu_waves_per_eu(QW == 1 ? (G * 2 + 3) / 4 : (G >= 4 ? 2 : 1)))) k_attn_pf(AttnArgs a) {
+  constexpr bool F8 = !std::is_same<ST, bf16>::value;
   constexpr int d = 128;
   constexpr int NW = G * 2 / QW;             // waves
   constexpr int NI_MAX = (16 * PF_SUB + NW - 1) / NW;   // staging instructions per wave and stage
   // one LDS array (a second __shared__ object can make hipcc drain the
   // prefetch early, cdna_hip_programming.md §5 trap 4a): 2 stages + row table
-  __shared__ __attribute__((aligned(16))) bf16 sm[PF_NS * PF_STAGE];
+  __shared__ __attribute__((aligned(16))) ST sm[PF_NS * PF_STAGE + (F8 ? PF_NS * 256 : 0)];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int ntile = (a.nq + PF_Q - 1) / PF_Q;
@@ -716,18 +788,37 @@ __global__ void __launch_bounds__(64 * G * 2 / QW) __attribute__((amdgpu_waves_p
     for (int qt = 0; qt < QW; ++qt) inq[qt] = qslot[qt] == slot;
     const long long cbase = (long long)a.layer * a.kv.s_layer + (long long)slot * a.kv.s_slot +
                             (long long)kh * a.kv.s_head;
-    const bf16* K = a.kv.k + cbase;    // [ctx][128]
-    const bf16* VB = a.kv.v + cbase;   // 32-position blocks of [128][32] (v_off)
+    const ST* K = kv_k<ST>(a) + cbase;    // [ctx][128]
+    const ST* VB = kv_v<ST>(a) + cbase;   // 32-position blocks of [128][32] (v_off)
+    const signed char* EK = F8 ? a.kv8.ek + cbase / d : nullptr;   // [ctx] row exponents
+    const signed char* EV = F8 ? a.kv8.ev + cbase / d : nullptr;
     auto issue = [&](int step) {
-      bf16* st = sm + (step % PF_NS) * PF_STAGE;
+      ST* st = sm + (step % PF_NS) * PF_STAGE;
 #pragma unroll
       for (int i = 0; i < NI_MAX; ++i)
         if (i < ni) {
-          const bf16* src = (((wave + NW * i) & 15) >= 8 ? VB : K) + (long long)step * 32 * PF_SUB * d + soff[i];
-          __builtin_amdgcn_global_load_lds((const void*)src,
-                                           (__attribute__((address_space(3))) void*)(st + (wave + NW * i) * 512),
-                                           16, 0, 0);
+          const ST* src = (((wave + NW * i) & 15) >= 8 ? VB : K) + (long long)step * 32 * PF_SUB * d + soff[i];
+          if constexpr (F8) {
+            __builtin_amdgcn_global_load_lds((const void*)src,
+                                             (__attribute__((address_space(3))) void*)(st + (wave + NW * i) * 512),
+                                             4, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void*)(src + 4),
+                                             (__attribute__((address_space(3))) void*)(st + (wave + NW * i) * 512 + 256),
+                                             4, 0, 0);
+          } else {
+            __builtin_amdgcn_global_load_lds((const void*)src,
+                                             (__attribute__((address_space(3))) void*)(st + (wave + NW * i) * 512),
+                                             16, 0, 0);
+          }
         }
+      if constexpr (F8) {
+        if (wave == NW - 1) {   // the stage's exponents: [K of its 32 PF_SUB keys | V | unused]
+          const signed char* src = ((lane & 16) ? EV : EK) + step * 32 * PF_SUB + (lane & 15) * 4;
+          __builtin_amdgcn_global_load_lds((const void*)src,
+                                           (__attribute__((address_space(3))) void*)(sm + PF_NS * PF_STAGE + (step % PF_NS) * 256),
+                                           4, 0, 0);
+        }
+      }
     };
     for (int p = 0; p < PF_NS - 1 && p < nsteps; ++p) issue(p);
     for (int step = 0; step < nsteps; ++step) {
@@ -742,11 +833,11 @@ __global__ void __launch_bounds__(64 * G * 2 / QW) __attribute__((amdgpu_waves_p
       for (int sub = 0; sub < PF_SUB; ++sub) {
       const int k0 = (step * PF_SUB + sub) * 32;
       if (k0 >= nk) break;
-      const bf16* st = sm + (step % PF_NS) * PF_STAGE + sub * 16 * 512;
+      const ST* st = sm + (step % PF_NS) * PF_STAGE + sub * 16 * 512;
       // all 8 K fragments, then the 16 S MFMAs (one LDS round trip, not one per key tile)
       bf16x8 kf[8];
 #pragma unroll
-      for (int f = 0; f < 8; ++f) kf[f] = *(const bf16x8*)(st + f * 512 + lane * 8);
+      for (int f = 0; f < 8; ++f) kf[f] = pf_frag(st + f * 512, lane);
       f32x4 s[2][QW];
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
@@ -760,7 +851,19 @@ __global__ void __launch_bounds__(64 * G * 2 / QW) __attribute__((amdgpu_waves_p
       // (read one at a time after it, each read's latency was exposed 8 times a step)
       bf16x8 vf[8];
 #pragma unroll
-      for (int dt = 0; dt < 8; ++dt) vf[dt] = *(const bf16x8*)(st + (8 + dt) * 512 + lane * 8);
+      for (int dt = 0; dt < 8; ++dt) vf[dt] = pf_frag(st + (8 + dt) * 512, lane);
+      u32x2 xk, xv;   // FP8: the exponents of the lane's keys 8g .. 8g+7
+      if constexpr (F8) {   // S^T row 4g+i of key tile kt is key 8g + 4kt + i: byte 4kt + i of the lane's K exponents
+        const ST* xs = sm + PF_NS * PF_STAGE + (step % PF_NS) * 256 + sub * 32 + 8 * g;
+        xk = *(const u32x2*)xs;
+        xv = *(const u32x2*)(xs + 32 * PF_SUB);
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int qt = 0; qt < QW; ++qt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[kt][qt][i] = ldexpf(s[kt][qt][i], exp_at(xk[kt], i));
+      }
       __builtin_amdgcn_sched_barrier(0);
       // online softmax with a lazy running max: a column's m (log2 units) moves
       // only when a score exceeds it by > PF_LAZY, so P <= 2^PF_LAZY and the
@@ -831,7 +934,8 @@ __global__ void __launch_bounds__(64 * G * 2 / QW) __attribute__((amdgpu_waves_p
               const float e = decltype(full_c)::value ? __builtin_fmaf(x[qt][kt][i], sl2, -mref) : x[qt][kt][i] - mref;
               const float p = __builtin_amdgcn_exp2f(e);
               ps += p;
-              pf[qt][4 * kt + i] = (bf16)p;
+              if constexpr (F8) pf[qt][4 * kt + i] = (bf16)ldexpf(p, exp_at(xv[kt], i));
+              else pf[qt][4 * kt + i] = (bf16)p;
             }
           l[qt] += ps;
         }
@@ -888,18 +992,19 @@ bool attn_use_prefill(int nq, int nslots) {
   return nq >= 256 && nq >= PF_Q * nslots;
 }
 
+template <class ST>
 static int launch_attn_pf(const AttnArgs& a, hipStream_t st) {
   const dim3 grid((a.nq + PF_Q - 1) / PF_Q, a.nkv);
   // two waves per head (QW = 1) while that keeps <= 3 waves per SIMD (G <= 6)
   switch (a.nh / a.nkv) {
-    case 1: hipLaunchKernelGGL((k_attn_pf<1, 1>), grid, dim3(128), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_attn_pf<2, 1>), grid, dim3(256), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_attn_pf<3, 1>), grid, dim3(384), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_attn_pf<4, 1>), grid, dim3(512), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_attn_pf<5, 1>), grid, dim3(640), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_attn_pf<6, 1>), grid, dim3(768), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_attn_pf<7, 2>), grid, dim3(448), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_attn_pf<8, 2>), grid, dim3(512), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_attn_pf<1, 1, ST>), grid, dim3(128), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_attn_pf<2, 1, ST>), grid, dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_attn_pf<3, 1, ST>), grid, dim3(384), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_attn_pf<4, 1, ST>), grid, dim3(512), 0, st, a); break;
+    case 5: hipLaunchKernelGGL((k_attn_pf<5, 1, ST>), grid, dim3(640), 0, st, a); break;
+    case 6: hipLaunchKernelGGL((k_attn_pf<6, 1, ST>), grid, dim3(768), 0, st, a); break;
+    case 7: hipLaunchKernelGGL((k_attn_pf<7, 2, ST>), grid, dim3(448), 0, st, a); break;
+    default: hipLaunchKernelGGL((k_attn_pf<8, 2, ST>), grid, dim3(512), 0, st, a); break;
   }
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
@@ -931,25 +1036,35 @@ int attn_plan(int nq, int nkv, int max_len, int* chunk) {
   return ns;
 }
 
-template <int NW>
+template <int NW, class ST>
 static void launch_attn_nw(const AttnArgs& a, dim3 grid, hipStream_t st) {
   const dim3 blk(64 * NW);
   switch (a.nh / a.nkv) {
-    case 1: hipLaunchKernelGGL((k_attn<1, NW>), grid, blk, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_attn<2, NW>), grid, blk, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_attn<3, NW>), grid, blk, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_attn<4, NW>), grid, blk, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_attn<5, NW>), grid, blk, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_attn<6, NW>), grid, blk, 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_attn<7, NW>), grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_attn<8, NW>), grid, blk, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_attn<1, NW, ST>), grid, blk, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_attn<2, NW, ST>), grid, blk, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_attn<3, NW, ST>), grid, blk, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_attn<4, NW, ST>), grid, blk, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((k_attn<5, NW, ST>), grid, blk, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((k_attn<6, NW, ST>), grid, blk, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((k_attn<7, NW, ST>), grid, blk, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_attn<8, NW, ST>), grid, blk, 0, st, a); break;
   }
+}
+template <class ST>
+static void launch_attn_st(const AttnArgs& a, dim3 grid, int nw, hipStream_t st) {
+  if (nw == 8) launch_attn_nw<8, ST>(a, grid, st);
+  else if (nw == 4) launch_attn_nw<4, ST>(a, grid, st);
+  else launch_attn_nw<2, ST>(a, grid, st);
 }
 
 int launch_attn(AttnArgs a, hipStream_t st) {
   if (a.nq <= 0) return 0;
   if (a.kv.d != 128 || a.nh % a.nkv || a.nh / a.nkv > ATT_GMAX) return 1;
-  if (a.prefill) return launch_attn_pf(a, st);
+  const bool f8 = a.kv8.k != nullptr;
+  if (f8 && (!a.kv8.v || !a.kv8.ek || !a.kv8.ev || a.kv.s_layer % 128 || a.kv.s_slot % 128 || a.kv.s_head % 128 ||
+             a.kv.max_ctx % 64))
+    return 1;
+  if (a.prefill) return f8 ? launch_attn_pf<unsigned char>(a, st) : launch_attn_pf<bf16>(a, st);
   if (a.chunk % ATT_KC || a.nsplit > ATT_SPLITS_MAX) return 1;
   if ((a.nsplit > 1 || a.defer) && (!a.part_o || !a.part_ml || !a.counters)) return 1;
   if (a.defer && a.nsplit > ATT_MERGE_IN) return 1;
@@ -960,10 +1075,40 @@ int launch_attn(AttnArgs a, hipStream_t st) {
   a.merge = !a.defer && !a.group && a.nsplit > (mi >= 0 ? mi : ATT_MERGE_IN) ? 1 : 0;
   dim3 grid(a.nsplit, a.nq * a.nkv);
   const int nw = a.chunk >= 256 ? 8 : a.chunk >= 128 ? 4 : 2;   // 32 keys per wave step
-  if (nw == 8) launch_attn_nw<8>(a, grid, st);
-  else if (nw == 4) launch_attn_nw<4>(a, grid, st);
-  else launch_attn_nw<2>(a, grid, st);
+  if (f8) launch_attn_st<unsigned char>(a, grid, nw, st);
+  else launch_attn_st<bf16>(a, grid, nw, st);
   if (a.merge) hipLaunchKernelGGL(k_attn_merge, dim3(a.nq * a.nh, 2), dim3(512), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// Diagnostic (vv_diag_attn_ctx): the merge o_proj's XF_ATTN_MERGE performs on a
+// deferred or grouped launch's partials, as a kernel of its own: out = sum_s
+// e^{m_s - M} o_s / sum_s e^{m_s - M} l_s over the row's active partials, in order.
+__global__ void __launch_bounds__(128) k_attn_finish(AttnArgs a) {
+  constexpr int d = 128;
+  const int qi = blockIdx.x / a.nh, h = blockIdx.x - qi * a.nh, j = threadIdx.x;
+  const int len = a.pos[qi] + 1;
+  const int chunk = row_chunk(a, len);
+  const int nact = (len + chunk - 1) / chunk;
+  const int np = a.group ? (nact + a.group - 1) / a.group : nact;
+  const int ld = a.group ? a.ngroups : a.nsplit;
+  const float* po = a.group ? a.part_o2 : a.part_o;
+  const float* pml = a.group ? a.part_ml2 : a.part_ml;
+  const long long p0 = ((long long)qi * a.nh + h) * ld;
+  float M = -INFINITY;
+  for (int s2 = 0; s2 < np; ++s2) M = fmaxf(M, pml[(p0 + s2) * 2]);
+  float num = 0.f, den = 0.f;
+  for (int s2 = 0; s2 < np; ++s2) {
+    const float w = __expf(pml[(p0 + s2) * 2] - M);
+    num += w * po[(p0 + s2) * d + j];
+    den += w * pml[(p0 + s2) * 2 + 1];
+  }
+  a.out[(long long)qi * a.nh * d + h * d + j] = tobf(num / den);
+}
+int launch_attn_finish(const AttnArgs& a, hipStream_t st) {
+  if (a.nq <= 0) return 0;
+  if (!a.defer && !a.group) return 1;
+  hipLaunchKernelGGL(k_attn_finish, dim3(a.nq * a.nh), dim3(128), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -34,6 +34,24 @@ DEV f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// 8 e4m3 codes (two dwords, ascending k) -> 8 bf16.  v_cvt_pk_f32_fp8 is exact
+// and an e4m3 value has 4 significant bits, so its f32 form has a zero low half:
+// the bf16 is the high half, no rounding.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+DEV bf16x8 cvt8(unsigned d0, unsigned d1) {
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
+  const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
+  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
+  const auto d = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
+  u32x4 o;
+  o[0] = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
+  o[1] = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
+  o[2] = (__float_as_uint(c[0]) >> 16) | (__float_as_uint(c[1]) & 0xffff0000u);
+  o[3] = (__float_as_uint(d[0]) >> 16) | (__float_as_uint(d[1]) & 0xffff0000u);
+  return __builtin_bit_cast(bf16x8, o);
+}
+
 // V cache of one (layer, slot, kv head): positions in blocks of 32, each block
 // [128 dims][32 positions] (8 KB contiguous) -- attention's P.V operand loads
 // (8 positions of one dim per lane) then read whole 1 KB pieces instead of

@@ -211,6 +211,19 @@ struct vv_ctx {
   // mfma_pack8 order) + <name>e (int8 row exponents) instead of the bf16 <name>
   bool quantized = false;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
+  // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
+  // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
+  int kv_dtype = 0;
+  DevBuf kv8_k, kv8_v, kv8_ek, kv8_ev;
+  KV8 kv8 = {nullptr, nullptr, nullptr, nullptr};
+  // the staged append of a pass: a one-slot bf16 cache over the pass's token indices
+  // (K | V), the cos / sin rows of the tokens' real positions, and the slot (all 0) /
+  // position (0, 1, ...) tables the q|k|v epilogue indexes it with
+  DevBuf kv_stage;
+  size_t kv_stage_tokens = 0;
+  KVLayout stg = {nullptr, nullptr, 0, 0, 0, 0, 0};
+  bf16* stg_cs = nullptr;
+  int *stg_slot = nullptr, *stg_pos = nullptr;
 };
 
 // ------------------------------------------------------------------ helpers
@@ -261,6 +274,28 @@ static int need_lm_w(vv_ctx* c, const std::string& n, int64_t N, int64_t K) {
   CHK(need(c, n + "8", {N, K}));
   CHK(need(c, n + "e", {N}));
   c->quantized = true;
+  return 0;
+}
+
+// FP8 KV: the staging cache for passes of up to ntok tokens (grown outside a hot
+// call only: vv_finalize sizes it for a decode pass, a longer prefill grows it and
+// bumps the workspace epoch through DevBuf::ensure)
+static int kv_stage_ensure(vv_ctx* c, size_t ntok) {
+  if (ntok <= c->kv_stage_tokens) return 0;
+  const size_t cap = (ntok + 31) / 32 * 32, d = 128, nkv = c->cfg.n_kv_heads;
+  const size_t kv_elems = nkv * cap * d;
+  CHK(c->kv_stage.ensure((2 * kv_elems + cap * d) * sizeof(bf16) + 2 * cap * sizeof(int)));
+  c->kv_stage_tokens = cap;
+  c->stg.k = (bf16*)c->kv_stage.p;
+  c->stg.v = c->stg.k + kv_elems;
+  c->stg.d = (int)d;
+  c->stg.max_ctx = (int)cap;
+  c->stg.s_head = (long long)(cap * d);
+  c->stg.s_slot = c->stg.s_head * (long long)nkv;
+  c->stg.s_layer = 0;
+  c->stg_cs = c->stg.v + kv_elems;
+  c->stg_slot = (int*)(c->stg_cs + cap * d);
+  c->stg_pos = c->stg_slot + cap;
   return 0;
 }
 
@@ -971,7 +1006,8 @@ void vv_destroy(vv_ctx* c) {
   DevBuf* bufs[] = {&c->norm_ws, &c->kv_k, &c->kv_v, &c->lm_ws, &c->attn_part, &c->attn_cnt, &c->valid_ids, &c->splitk_ws, &c->splitk_cnt,
                     &c->temb, &c->tfreq_tmp, &c->head_ws, &c->codec_ws, &c->slot_scratch, &c->unit_sb,
                     &c->rope_tab, &c->zero_rows, &c->hf_sync, &c->cs_sync, &c->m16_buf, &c->lf_sync,
-                    &c->cw_sync, &c->cw_slab, &c->cw_xbuf, &c->lf_slab, &c->la_part, &c->w8_scratch};
+                    &c->cw_sync, &c->cw_slab, &c->cw_xbuf, &c->lf_slab, &c->la_part, &c->w8_scratch,
+                    &c->kv8_k, &c->kv8_v, &c->kv8_ek, &c->kv8_ev, &c->kv_stage};
   for (DevBuf* b : bufs) b->release();
   ConvNet* nets[] = {&c->dec, &c->sem, &c->aenc, &c->senc};
   for (ConvNet* n : nets) {
@@ -989,6 +1025,24 @@ int vv_bind_weight(vv_ctx* c, const char* name, const void* p, const int64_t* sh
   w.p = p;
   w.shape.assign(shape, shape + ndim);
   c->w[name] = w;
+  return 0;
+}
+
+int vv_set_kv_dtype(vv_ctx* c, int dtype) {
+  if (!c) FAIL("vv_set_kv_dtype: null context");
+  if (c->finalized) FAIL("vv_set_kv_dtype after vv_finalize: the KV cache is already allocated");
+  if (dtype != 0 && dtype != 1)
+    FAIL("vv_set_kv_dtype: unsupported dtype " + std::to_string(dtype) + " (0 = bf16, 1 = fp8 e4m3)");
+  if (dtype && (c->tp_size > 1 || c->comm)) FAIL("an FP8 KV cache is not supported on a tensor-parallel engine");
+  c->kv_dtype = dtype;
+  return 0;
+}
+int vv_kv_dtype(vv_ctx* c) { return c ? c->kv_dtype : 0; }
+int vv_kv_bytes(vv_ctx* c, long long* bytes) {
+  if (!c || !bytes) FAIL("vv_kv_bytes: null argument");
+  if (!c->finalized) FAIL("vv_kv_bytes before vv_finalize: the KV cache is not allocated yet");
+  *bytes = (long long)(c->kv_k.bytes + c->kv_v.bytes + c->kv8_k.bytes + c->kv8_v.bytes + c->kv8_ek.bytes +
+                       c->kv8_ev.bytes);
   return 0;
 }
 
@@ -1112,8 +1166,28 @@ int vv_finalize(vv_ctx* c) {
   c->kv.s_slot = c->kv.s_head * k.n_kv_heads;
   c->kv.s_layer = c->kv.s_slot * c->lm_slots;
   const size_t kvb = (size_t)c->kv.s_layer * k.n_layers * sizeof(bf16);
-  CHK(c->kv_k.ensure(kvb));
-  CHK(c->kv_v.ensure(kvb + 256));
+  if (c->kv_dtype) {
+    // FP8 e4m3: one byte per element in the same geometry + one int8 exponent per row
+    if (c->tp_size > 1 || c->comm) FAIL("an FP8 KV cache is not supported on a tensor-parallel engine");
+    if (d != 128) FAIL("an FP8 KV cache needs head_dim 128");
+    const size_t codes = kvb / sizeof(bf16), exps = codes / d;
+    CHK(c->kv8_k.ensure(codes));
+    CHK(c->kv8_v.ensure(codes + 256));
+    CHK(c->kv8_ek.ensure(exps));
+    CHK(c->kv8_ev.ensure(exps));
+    HIPCHK(hipMemset(c->kv8_k.p, 0, c->kv8_k.bytes));
+    HIPCHK(hipMemset(c->kv8_v.p, 0, c->kv8_v.bytes));
+    HIPCHK(hipMemset(c->kv8_ek.p, 0, exps));
+    HIPCHK(hipMemset(c->kv8_ev.p, 0, exps));
+    c->kv8.k = (unsigned char*)c->kv8_k.p;
+    c->kv8.v = (unsigned char*)c->kv8_v.p;
+    c->kv8.ek = (signed char*)c->kv8_ek.p;
+    c->kv8.ev = (signed char*)c->kv8_ev.p;
+    CHK(kv_stage_ensure(c, (size_t)c->lm_slots));
+  } else {
+    CHK(c->kv_k.ensure(kvb));
+    CHK(c->kv_v.ensure(kvb + 256));
+  }
   // RoPE cos / sin per position (the q|k|v epilogue reads it instead of cosf / sinf)
   if (d == 128) {
     CHK(c->rope_tab.ensure((size_t)c->kv.max_ctx * 128 * sizeof(bf16)));
@@ -1185,12 +1259,17 @@ int vv_set_schedule(vv_ctx* c, int steps, const float* coef, const void* tfreq, 
 
 int vv_kv_copy(vv_ctx* c, int n, const int* slots, const int* src, const int* dst, vv_stream vst) {
   if (!c->finalized) FAIL("vv_kv_copy before vv_finalize");
+  if (c->kv_dtype) {
+    KCHK(launch_kv_copy8(c->kv, c->kv8, c->cfg.n_layers, c->cfg.n_kv_heads, n, slots, src, dst, (hipStream_t)vst));
+    return 0;
+  }
   KCHK(launch_kv_copy(c->kv, c->cfg.n_layers, c->cfg.n_kv_heads, n, slots, src, dst, (hipStream_t)vst));
   return 0;
 }
 
 int vv_kv_synthetic(vv_ctx* c, int n, const int* slots, int p0, int p1, unsigned seed, vv_stream vst) {
   if (!c->finalized) FAIL("vv_kv_synthetic before vv_finalize");
+  if (c->kv_dtype) FAIL("vv_kv_synthetic: the synthetic fill (k_kv_fill) writes a bf16 cache; this engine's KV cache is FP8 e4m3");
   if (p0 < 0 || p1 > c->cfg.max_ctx || p0 > p1) FAIL("vv_kv_synthetic: positions outside [0, max_ctx)");
   KCHK(launch_kv_fill(c->kv, c->cfg.n_layers, c->cfg.n_kv_heads, n, slots, p0, p1, seed, (hipStream_t)vst));
   return 0;
@@ -1315,6 +1394,7 @@ static int lm_begin(vv_ctx* c, LmPass& P, int ntok, const void* embeds, int embe
   const vv_config& k = c->cfg;
   const int H = k.hidden, d = k.head_dim, I = k.intermediate, nhd = k.n_heads * d;
   const size_t per = (size_t)H * 3 + c->qkv_n + nhd * 2 + I;
+  if (c->kv_dtype) CHK(kv_stage_ensure(c, (size_t)ntok));
   if ((size_t)ntok > c->lm_ws_tokens) {
     // + 16 act rows: a packed act block (vv_norm_pack) rounds the rows up to 16
     CHK(c->lm_ws.ensure((per * ntok + (size_t)16 * I) * sizeof(bf16) + 256));
@@ -1376,7 +1456,7 @@ extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launche
 }
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  return g_lm_attn && !c->quantized && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
+  return g_lm_attn && !c->quantized && !c->kv_dtype && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, LA_MAX_KEYS) &&
          lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
@@ -1411,6 +1491,17 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     g.rope.inv_freq = P.inv_freq;
     g.rope.cs_tab = g_rope_tab ? (const bf16*)c->rope_tab.p : nullptr;
     g.rope.kv = c->kv;
+    if (c->kv_dtype) {
+      // FP8 KV: the epilogue appends to the staging cache (token m at slot 0, position m; cos / sin
+      // from the pass's rows of the real positions), k_kv_quant below moves the rows to the cache
+      if (l == 0)
+        KCHK(launch_kv_stage_prep(P.ntok, (int)c->kv_stage_tokens, P.pos, c->kv.max_ctx, (const bf16*)c->rope_tab.p, c->stg_cs, c->stg_slot,
+                                  c->stg_pos, st));
+      g.rope.slots = c->stg_slot;
+      g.rope.pos = c->stg_pos;
+      g.rope.cs_tab = c->stg_cs;
+      g.rope.kv = c->stg;
+    }
     if (lm_attn_on(c, P)) {
       LmAttnArgs a;
       memset(&a, 0, sizeof(a));
@@ -1432,9 +1523,12 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       return 0;
     }
     CHK(gemm(c, g, st));
+    if (c->kv_dtype)
+      KCHK(launch_kv_quant(c->stg, c->kv, c->kv8, l, k.n_kv_heads, c->lm_slots, P.ntok, P.slot, P.pos, st));
   }
   AttnArgs at;
   memset(&at, 0, sizeof(at));
+  at.kv8 = c->kv8;
   at.stamps = g_attn_stamps;
   at.nq = P.ntok;
   at.nh = k.n_heads;
@@ -1661,6 +1755,7 @@ int vv_tp_unique_id(void* out, int nbytes) {
 
 int vv_tp_init(vv_ctx* c, int rank, int size, const void* unique_id) {
   if (size < 1 || rank < 0 || rank >= size) FAIL("vv_tp_init: bad rank / size");
+  if (size > 1 && c->kv_dtype) FAIL("vv_tp_init: an FP8 KV cache is not supported on a tensor-parallel engine");
   c->tp_rank = rank;
   c->tp_size = size;
   if (!unique_id) return 0;  // group emulation in one process: no communicator
@@ -2443,6 +2538,7 @@ int vv_diag_lm_qkv(vv_ctx* c, int ntok, int layer, const int* slots, const int* 
   const vv_config& k = c->cfg;
   if (ntok < 1 || (size_t)ntok > c->lm_ws_tokens) FAIL("vv_diag_lm_qkv: no such pass");
   if (layer < 0 || layer >= k.n_layers) FAIL("vv_diag_lm_qkv: bad layer");
+  if (c->kv_dtype) FAIL("vv_diag_lm_qkv reads a bf16 KV cache; this engine's is FP8 e4m3 (vv_diag_kv_read)");
   HIPCHK(hipDeviceSynchronize());
   const int H = k.hidden, d = k.head_dim, nhd = k.n_heads * d;
   const bf16* q = (const bf16*)c->lm_ws.p + (size_t)ntok * (2 * (size_t)H + c->qkv_n);
@@ -2459,6 +2555,88 @@ int vv_diag_lm_qkv(vv_ctx* c, int ntok, int layer, const int* slots, const int* 
       HIPCHK(hipMemcpy2D(vo, sizeof(bf16), c->kv.v + v0, 32 * sizeof(bf16), sizeof(bf16), d, hipMemcpyDeviceToDevice));
     }
   }
+  return 0;
+}
+
+// Diagnostics: positions [p0, p1) of `slot` as bf16 rows [layer][kv_head][p][128] (device
+// memory), K and V: read returns the cached values (dequantised under FP8 KV), write stores
+// rows (quantised under FP8 KV).  Synchronous.
+static int diag_kv_rows(vv_ctx* c, int slot, int p0, int p1, void* k_rows, void* v_rows, int write, const char* who) {
+  if (!c || !c->finalized || !k_rows || !v_rows) FAIL(std::string(who) + ": bad arguments");
+  if (slot < 0 || slot >= c->lm_slots || p0 < 0 || p1 > c->cfg.max_ctx || p0 > p1)
+    FAIL(std::string(who) + ": slot / positions out of range");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());
+  KCHK(launch_kv_rows(c->kv, c->kv8, c->cfg.n_layers, c->cfg.n_kv_heads, slot, p0, p1, (bf16*)k_rows, (bf16*)v_rows,
+                      write, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+int vv_diag_kv_read(vv_ctx* c, int slot, int p0, int p1, void* k_out, void* v_out) {
+  return diag_kv_rows(c, slot, p0, p1, k_out, v_out, 0, "vv_diag_kv_read");
+}
+int vv_diag_kv_write(vv_ctx* c, int slot, int p0, int p1, const void* k_in, const void* v_in) {
+  return diag_kv_rows(c, slot, p0, p1, const_cast<void*>(k_in), const_cast<void*>(v_in), 1, "vv_diag_kv_write");
+}
+
+// Diagnostic: only the attention launch of `layer` over the context's own cache, no append:
+// nq query rows q [nq][n_heads * 128] (device) at (slots[i], pos[i]) (device tables; row i
+// attends keys [0, pos[i]]) -> out [nq][n_heads * 128].  form: 0 = the decode kernel as
+// launch_attn plans it (splits by vv_attn_tune; in-kernel merge or k_attn_merge), 1 = the
+// prefill kernel, 2 = decode with the deferred merge (<= 8 splits), 3 = decode with the
+// grouped merge (groups of 2 splits, <= 8 groups); 2 and 3 leave partials that o_proj merges
+// in a pass -- here a diagnostic kernel merges them (launch_attn_finish).
+int vv_diag_attn_ctx(vv_ctx* c, int layer, int nq, const void* q, const int* slots, const int* pos, int form,
+                     void* out, vv_stream vst) {
+  if (!c || !c->finalized || !q || !slots || !pos || !out || nq < 1) FAIL("vv_diag_attn_ctx: bad arguments");
+  const vv_config& k = c->cfg;
+  if (layer < 0 || layer >= k.n_layers) FAIL("vv_diag_attn_ctx: bad layer");
+  if (form < 0 || form > 3) FAIL("vv_diag_attn_ctx: form must be 0..3");
+  hipStream_t st = (hipStream_t)vst;
+  std::vector<int> hp(nq), hs(nq);
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(hp.data(), pos, nq * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hs.data(), slots, nq * sizeof(int), hipMemcpyDeviceToHost));
+  int maxp = 0;
+  for (int i = 0; i < nq; ++i) {
+    if (hs[i] < 0 || hs[i] >= c->lm_slots || hp[i] < 0 || hp[i] >= k.max_ctx) FAIL("vv_diag_attn_ctx: bad slot / position");
+    maxp = std::max(maxp, hp[i] + 1);
+  }
+  const int d = k.head_dim;
+  AttnArgs at;
+  memset(&at, 0, sizeof(at));
+  at.kv8 = c->kv8;
+  at.kv = c->kv;
+  at.nq = nq;
+  at.nh = k.n_heads;
+  at.nkv = k.n_kv_heads;
+  at.layer = layer;
+  at.prefill = form == 1;
+  at.nsplit = at.prefill ? 1 : attn_plan(nq, k.n_kv_heads, maxp, &at.chunk);
+  if (at.prefill) at.chunk = 64;
+  at.defer = form == 2;
+  if (form == 2 && (at.nsplit < 2 || at.nsplit > 8)) FAIL("vv_diag_attn_ctx: the deferred merge takes 2..8 splits");
+  if (form == 3) {
+    at.group = 2;
+    at.ngroups = (at.nsplit + 1) / 2;
+    if (at.nsplit < 2 || at.ngroups > 8) FAIL("vv_diag_attn_ctx: the grouped merge takes 2..16 splits");
+  }
+  if ((size_t)nq * k.n_kv_heads * std::max(1, at.ngroups) > 65536) FAIL("attention split tickets exhausted");
+  CHK(c->attn_part.ensure((size_t)nq * k.n_heads * (at.nsplit + at.ngroups) * (d + 2) * sizeof(float)));
+  at.counters = (unsigned*)c->attn_cnt.p;
+  at.scale = 1.0f / sqrtf((float)d);
+  at.q = (const bf16*)q;
+  at.out = (bf16*)out;
+  at.slots = slots;
+  at.pos = pos;
+  at.part_o = (float*)c->attn_part.p;
+  at.part_ml = at.part_o + (size_t)nq * k.n_heads * at.nsplit * d;
+  if (at.group) {
+    at.part_o2 = at.part_ml + (size_t)nq * k.n_heads * at.nsplit * 2;
+    at.part_ml2 = at.part_o2 + (size_t)nq * k.n_heads * at.ngroups * d;
+  }
+  KCHK(launch_attn(at, st));
+  if (at.defer || at.group) KCHK(launch_attn_finish(at, st));
   return 0;
 }
 

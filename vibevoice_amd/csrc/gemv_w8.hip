@@ -46,21 +46,7 @@ constexpr size_t W8_LDS_MAX = 98304;     // A rows staged per K block (dynamic L
 
 DEV u32x4 ldw8(const unsigned char* p) { return __builtin_nontemporal_load((const u32x4*)p); }
 
-// 8 e4m3 codes (two dwords, ascending k) -> 8 bf16.  v_cvt_pk_f32_fp8 is exact
-// and an e4m3 value has 4 significant bits, so its f32 form has a zero low half:
-// the bf16 is the high half, no rounding.
-DEV bf16x8 cvt8(unsigned d0, unsigned d1) {
-  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false);
-  const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
-  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false);
-  const auto d = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
-  u32x4 o;
-  o[0] = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
-  o[1] = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
-  o[2] = (__float_as_uint(c[0]) >> 16) | (__float_as_uint(c[1]) & 0xffff0000u);
-  o[3] = (__float_as_uint(d[0]) >> 16) | (__float_as_uint(d[1]) & 0xffff0000u);
-  return __builtin_bit_cast(bf16x8, o);
-}
+// e4m3 -> bf16: cvt8 (common.h)
 
 DEV int w8_part(int len, int i, int n) { return (int)((unsigned)(len * i) / (unsigned)n); }
 

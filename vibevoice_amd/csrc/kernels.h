@@ -19,6 +19,18 @@ struct KVLayout {
   int d, max_ctx;
 };
 
+// FP8 (OCP e4m3) KV cache (kv_fp8.hip): one-byte codes in the geometry of the
+// bf16 cache -- a KVLayout's strides count elements, so they serve both -- and
+// one int8 exponent per cached row (the 128 values of one layer, slot, kv head
+// and position; value = code * 2^e) in side arrays [layer][slot][kv_head][ctx],
+// whose strides are the KVLayout's / 128.
+struct KV8 {
+  unsigned char* k;
+  unsigned char* v;
+  signed char* ek;
+  signed char* ev;
+};
+
 // A-operand transform (XF_*).  XF_NORM: inverse RMS of each A row over K, then
 // bf16(bf16(x * inv) * w) (w optional) and optionally the adaLN modulate
 // bf16(bf16(y * bf16(1 + scale)) + shift) with shift/scale read from `mod` rows.
@@ -188,6 +200,7 @@ struct AttnArgs {
   int ngroups;
   float* part_o2;
   float* part_ml2;
+  KV8 kv8;              // kv8.k != nullptr: the FP8 cache (kv.k / kv.v unused, kv's strides and max_ctx hold)
 };
 
 // out_r = sum_r in_r for every r (single-process tensor-parallel group)
@@ -443,6 +456,23 @@ int launch_kv_fill(KVLayout kv, int n_layers, int nkv, int n, const int* slots, 
                    hipStream_t st);
 int launch_kv_copy(KVLayout kv, int n_layers, int nkv, int n, const int* slots, const int* src, const int* dst,
                    hipStream_t st);
+// diagnostics (vv_diag_attn_ctx): out rows from the partials a deferred (a.defer) or grouped
+// (a.group) launch_attn left, merged as o_proj's XF_ATTN_MERGE would
+int launch_attn_finish(const AttnArgs& a, hipStream_t st);
+// ---- FP8 KV cache (kv_fp8.hip)
+// the pass's staging tables: cs[m] = rope_tab[pos[m]] (256 B rows, m < ntok), stg_slot[m] = 0, stg_pos[m] = m (m < cap)
+int launch_kv_stage_prep(int ntok, int cap, const int* pos, int max_ctx, const bf16* rope_tab, bf16* cs,
+                         int* stg_slot, int* stg_pos, hipStream_t st);
+// rows of the ntok staged tokens (staging: a one-slot bf16 cache, token m at position m) ->
+// codes + exponents of `layer` at (slots[m], pos[m]); kv gives the cache's strides
+int launch_kv_quant(KVLayout stg, KVLayout kv, KV8 kv8, int layer, int nkv, int nslots, int ntok, const int* slots,
+                    const int* pos, hipStream_t st);
+int launch_kv_copy8(KVLayout kv, KV8 kv8, int n_layers, int nkv, int n, const int* slots, const int* src,
+                    const int* dst, hipStream_t st);
+// diagnostics: positions [p0, p1) of one slot <-> bf16 rows [layer][kv_head][p][128] (K and V),
+// for either cache (kv8.k == nullptr: the bf16 cache); write quantises under FP8
+int launch_kv_rows(KVLayout kv, KV8 kv8, int n_layers, int nkv, int slot, int p0, int p1, bf16* k_rows, bf16* v_rows,
+                   int write, hipStream_t st);
 int launch_final_head(int R, int H, const bf16* h, const int* idx, const bf16* norm_w, float eps, bf16* hidden_out,
                       const bf16* W, const int* ids, int nid, float* logits, hipStream_t st);
 int launch_lmhead_ids(int R, int H, const bf16* h, long long ldh, const bf16* W, const int* ids, int nid, float* out,

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import W8_CODES, check_weight_dtype, codec_channels, head_tp_check, pack
+from .weights import W8_CODES, check_kv_dtype, check_weight_dtype, codec_channels, head_tp_check, pack
 
 _VALID_IDS_DEFAULT = None
 
@@ -76,7 +76,7 @@ class Engine:
 
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
-                 persistent=True, weight_dtype=None):
+                 persistent=True, weight_dtype=None, kv_dtype=None):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -92,9 +92,13 @@ class Engine:
         kernels and never demotes it).
         weight_dtype: None = bf16 weights; "fp8_e4m3" = the LM projections as
         OCP e4m3 codes + a power-of-two scale per row (weights.pack; tp_size 1
-        only).  With `packed`, the format is the one those weights were packed in."""
+        only).  With `packed`, the format is the one those weights were packed in.
+        kv_dtype: None = a bf16 KV cache; "fp8_e4m3" = K and V stored as OCP e4m3
+        codes + a power-of-two scale per cached row (vv_set_kv_dtype; tp_size 1 only)."""
         persistent = normalize_persistent(persistent)
         check_weight_dtype(weight_dtype, tp_size)
+        check_kv_dtype(kv_dtype, tp_size)
+        self.kv_dtype = kv_dtype
         L = _lib.lib()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -128,6 +132,8 @@ class Engine:
                     _lib.check(L.vv_tp_shard_head(h, 1), "tp_shard_head")
             if persistent is not True:
                 _lib.check(L.vv_set_persistent(h, 2 if persistent == "follow" else 0), "set_persistent")
+            if kv_dtype is not None:
+                _lib.check(L.vv_set_kv_dtype(h, 1), "set_kv_dtype")
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")
@@ -170,6 +176,12 @@ class Engine:
         """Zero every grid-wait counter of this context (vv_sync_reset; after a
         wait gave up).  Synchronises the device."""
         _lib.check(_lib.lib().vv_sync_reset(self.h), "sync_reset")
+
+    def kv_bytes(self):
+        """Device bytes of the LM's KV cache (exponents included under FP8 KV)."""
+        n = ctypes.c_longlong()
+        _lib.check(_lib.lib().vv_kv_bytes(self.h, ctypes.byref(n)), "kv_bytes")
+        return n.value
 
     def weights_quantized(self):
         return _lib.lib().vv_weights_quantized(self.h) == 1

@@ -99,8 +99,10 @@ class _SlotPool:
             # (persistent="follow": this codec context runs the owner's one-launch
             # kernels -- bit-identical to its codec step -- without registering, so
             # it never demotes the owner's context)
+            # (kv_dtype=None whatever the owner's: this context runs no LM pass, its 64-position cache is idle)
             self._eng = Engine(self.model.config, None, m.device, max_batch=self.n, max_ctx=64, packed=m.w,
-                               tp_rank=m.tp_rank, tp_size=m.tp_size, tp_head=m.tp_head, persistent="follow")
+                               tp_rank=m.tp_rank, tp_size=m.tp_size, tp_head=m.tp_head, persistent="follow",
+                               kv_dtype=None)
         return self._eng
 
     def _i32(self, xs):

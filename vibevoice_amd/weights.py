@@ -220,6 +220,18 @@ def check_weight_dtype(weight_dtype, tp_size=1):
     return weight_dtype
 
 
+KV_DTYPES = (None, "fp8_e4m3")
+
+
+def check_kv_dtype(kv_dtype, tp_size=1):
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype={kv_dtype!r} is not supported; supported: {list(KV_DTYPES)}")
+    if kv_dtype is not None and tp_size > 1:
+        raise ValueError(f"kv_dtype={kv_dtype!r} is not supported with tensor parallelism "
+                         f"(tp_size={tp_size}); use a bf16 KV cache or tp_size=1")
+    return kv_dtype
+
+
 def quantize_rows_e4m3(w):
     """[N, K] -> (codes [N, K] torch.float8_e4m3fn (OCP), e [N] int8) with
     w ~ codes * 2**e[n]: e[n] is the smallest integer with amax(row) / 2**e <= 448
@@ -238,6 +250,16 @@ def quantize_rows_e4m3(w):
 def dequantize_rows(codes, e):
     """codes * 2**e[n] as bf16; exact (4 significant bits, a power-of-two scale)."""
     return torch.ldexp(codes.float(), e.to(torch.int32)[:, None]).to(torch.bfloat16)
+
+
+def fake_quantize_kv(x):
+    """[..., 128] bf16 -> bf16: every row (the 128 values of one layer, slot, kv
+    head and position; K after RoPE, V as projected) replaced by what the FP8
+    KV cache holds for it, quantize_rows_e4m3 then dequantize_rows.  The CPU
+    statement of the format csrc/kv_fp8.hip stores."""
+    assert x.dtype == torch.bfloat16 and x.shape[-1] == 128, (x.dtype, tuple(x.shape))
+    codes, e = quantize_rows_e4m3(x.reshape(-1, 128))
+    return dequantize_rows(codes, e).reshape(x.shape)
 
 
 def mfma_pack8(c):
