@@ -171,9 +171,12 @@ int vv_embed(vv_ctx* ctx, int n, const int* ids, void* embeds_out, vv_stream st)
 int vv_diffusion_sample(vv_ctx* ctx, int n, const void* pos_h, const void* neg_h, void* x_io, float cfg_scale,
                         const float* sde_noise, vv_stream st);
 /* Grid-waiting kernels.  Where this context is the device's only one with them
- * enabled, the LM MLP block at B = 1 (k_lm_ffn), each diffusion-head FFN layer
- * at 2 <= 2n <= 16 rows (k_head_m16) and the codec's C = 2,048 / 1,024 stages
- * of one sample (k_codec_stage*) each run as ONE launch of one workgroup per CU
+ * enabled, the LM's attention half at decode (k_lm_attn, <= 16 rows), its MLP
+ * block at B = 1 (k_lm_ffn) and at 3..16 rows (k_lm_ffn16), each diffusion-head
+ * FFN layer at 2 <= 2n <= 16 rows (k_head_m16), the codec's C = 2,048 / 1,024
+ * stages of one sample (k_codec_stage, k_codec_stage_s) and its C = 256 / 512
+ * stages (k_codec_wide: waits inside clusters of workgroups) each run as ONE
+ * launch of at most one workgroup per CU
  * whose workgroups wait for each other inside the launch (bounded, ~200 ms;
  * the occupancy query must show the whole grid co-resident, else the GEMV
  * launches run).  If a wait ever gave up (workgroups not co-resident, e.g.

@@ -195,12 +195,19 @@ int vv_head_m16_pre(int on);
 int vv_head_layers_replay(vv_ctx* ctx, int n, const void* pos_h, const void* neg_h, int reps, vv_stream st);
 /* Test hook: raise the engine's grid-wait error word as a wait that gave up
  * would, and leave its wait counters part-advanced as such a launch does
- * (synchronises the device first). */
+ * (synchronises the device first): in each of the three counter buffers shard 0,
+ * every generation line and one ticket word of csrc/sync_layout.h's table; in
+ * the wide codec stages' buffer the first cluster counter of each C. */
 int vv_diag_raise_sync_error(vv_ctx* ctx);
-/* Test hook: word 0 of the 13 counter lines of each wait family (head, codec
- * stage, LM MLP) into out[39]; consistent between launches when every shard
- * line (0-7) is a multiple of 32 and every generation line a multiple of 8. */
-int vv_diag_sync_words(vv_ctx* ctx, unsigned* out);
+/* Test hook: the wait counters (csrc/sync_layout.h) into out[53]; n is the
+ * caller's capacity in words (fails, writing nothing, when n < 53).  Per buffer
+ * (head, codec stage, LM: 17 words each): word 0 of each of the 16 lines, then
+ * max(ticket % 4) over the 48 ticket words.  Then, for the wide codec stages'
+ * buffer, max(counter % S) over the 256 cluster counters of C = 256 (S = 8) and
+ * of C = 512 (S = 16).  Consistent between launches: every shard line (0-7) a
+ * multiple of 32, every generation line (11, 12, 15) a multiple of 8, the three
+ * residues 0. */
+int vv_diag_sync_words(vv_ctx* ctx, unsigned* out, int n);
 /* The rule every grid-waiting launch applies (kernels.h persist_resident + the
  * context half): 1 when a grid of `grid` one-per-CU workgroups with the
  * occupancy query's blocks_per_cu on `cus` CUs and `scratch_bytes` of scratch

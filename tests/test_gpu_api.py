@@ -19,6 +19,7 @@ import pytest
 import torch
 from safetensors.torch import save_file
 
+from sync_counters import assert_counters_consistent
 from tiny import tiny_config, tiny_dict
 from vibevoice_amd.modeling_vibevoice_inference import VibeVoiceForConditionalGenerationInference
 from vibevoice_amd.synthetic import tokenizer_ids
@@ -148,27 +149,12 @@ def test_grid_wait_error_raises_before_audio_is_streamed():
             sess.result() if end_with_result else sess.step()
         assert [len(c) for c in st.chunks] == [3, 3]          # step 3's chunk never reached the streamer
         assert not sess.step()                                # the session is over
-        _assert_counters_consistent(m)                        # vv_sync_reset ran before the raise
+        assert_counters_consistent(m.engine)                  # vv_sync_reset ran before the raise
         # the word was reset by its read-back: a fresh session runs clean
         st2 = RecordingStreamer(2)
         out = m.generate(input_ids=ids, attention_mask=mask, tokenizer=TOK, cfg_scale=1.3,
                          forced_tokens=[[D, D, X]] * 2, audio_streamer=st2, show_progress_bar=False)
         assert [len(c) for c in st2.chunks] == [2, 2] and out.speech_outputs[0].shape[-1] == 2 * m.engine.hop
-
-
-def _assert_counters_consistent(m):
-    """vv_diag_sync_words: every shard line a multiple of 32 arrivals, every
-    generation line a multiple of 8 -- the state between two launches.  The
-    raise hook leaves shard 0 at +5 and the generations at +3, as a launch that
-    gave up does; only vv_sync_reset makes them consistent again."""
-    import ctypes
-    from vibevoice_amd import _lib
-    words = (ctypes.c_uint * 39)()
-    _lib.check(_lib.lib().vv_diag_sync_words(m.engine.h, words), "sync_words")
-    for fam in range(3):
-        w = list(words[fam * 13:(fam + 1) * 13])
-        assert all(v % 32 == 0 for v in w[:8]), (fam, w)
-        assert w[11] % 8 == 0 and w[12] % 8 == 0, (fam, w)
 
 
 def test_grid_wait_error_on_the_last_step_without_streamer():
@@ -196,7 +182,7 @@ def test_grid_wait_error_on_the_last_step_without_streamer():
     assert sess.step()                     # the last diffusion step before result(): no read-back after it
     with pytest.raises(RuntimeError, match="grid wait gave up"):
         sess.result()
-    _assert_counters_consistent(m)
+    assert_counters_consistent(m.engine)
     again = run()
     assert torch.equal(clean.sequences, again.sequences)
     for b in range(2):

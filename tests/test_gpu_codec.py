@@ -14,6 +14,7 @@ import torch
 from gpu_util import cos, rel_err
 from oracle import codec as ocodec
 from oracle import lm as olm
+from sync_counters import assert_counters_consistent
 from tiny import tiny_config
 from vibevoice_amd.engine import Engine
 from vibevoice_amd.weights import synthetic_state_dict
@@ -199,6 +200,7 @@ def test_codec_stage_persistent_launch():
     finally:
         L.vv_codec_stage(1)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
     st_a, st_s = ocodec.StreamState(2), ocodec.StreamState(2)
     idx = torch.tensor([1])
     for f, lat in enumerate(lats):
@@ -366,6 +368,7 @@ def test_codec_wide_stages(n):
         L.vv_codec_wide(1)
         L.vv_codec_wide_over(0)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
     st_a, st_s = ocodec.StreamState(max(2, n)), ocodec.StreamState(max(2, n))
     idx = torch.arange(n)
     for f, lat in enumerate(lats):

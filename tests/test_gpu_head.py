@@ -15,6 +15,7 @@ import torch
 from golden_io import load, t, weights
 from gpu_util import cos, rel_err
 from oracle import head as ohead
+from sync_counters import assert_counters_consistent
 from tiny import tiny_config
 from vibevoice_amd.engine import Engine
 from vibevoice_amd.weights import synthetic_state_dict
@@ -268,6 +269,7 @@ def test_head_m16_vs_oracle_and_gemv_pair(n):
         L.vv_head_m16(1)
         L.vv_head_m16_pre(1)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
     m16, pair, whole = outs[1][0], outs[0][0], outs[3][0]
     e, ep, eb = rel_err(m16, ref), rel_err(pair, ref), rel_err(m16, pair)
     ew, ewd = rel_err(whole, ref), rel_err(m16, whole)

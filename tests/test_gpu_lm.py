@@ -13,6 +13,7 @@ import torch
 from golden_io import load, t, weights
 from gpu_util import cos, kv_synthetic, rel_err
 from oracle import lm as olm
+from sync_counters import assert_counters_consistent
 from tiny import tiny_config
 from vibevoice_amd.engine import Engine
 from vibevoice_amd.weights import synthetic_state_dict
@@ -278,6 +279,7 @@ def test_lm_ffn_one_launch_vs_oracle_and_gemv_pair():
     finally:
         L_.vv_lm_ffn(1)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
 
 
 @pytest.mark.parametrize("n", [8, 3])
@@ -332,6 +334,7 @@ def test_lm_ffn16_one_launch_vs_oracle_and_gemv_pair(n):
     finally:
         L_.vv_lm_ffn(1)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
 
 
 @pytest.mark.parametrize("n,lens", [(1, [600, 33]), (3, [1, 31, 32, 64, 200, 97]),
@@ -389,6 +392,7 @@ def test_lm_attn_one_launch_vs_oracle_and_three_launches(n, lens):
     finally:
         L_.vv_lm_attn(1)
     eng.check_sync()
+    assert_counters_consistent(eng)   # a clean run leaves every wait counter at a whole number of waits
 
 
 def test_lm_attn_one_launch_limits():

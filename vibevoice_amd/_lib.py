@@ -115,7 +115,7 @@ EXPORTS = [
     ("vv_sync_error", I, [P]),
     ("vv_sync_error_async", I, [P, P, P]),
     ("vv_diag_raise_sync_error", I, [P]),
-    ("vv_diag_sync_words", I, [P, P]),
+    ("vv_diag_sync_words", I, [P, P, I]),
     ("vv_sync_reset", I, [P]),
     ("vv_set_persistent", I, [P, I]),
     ("vv_persist_decision", I, [I, I, I, I, I, I]),

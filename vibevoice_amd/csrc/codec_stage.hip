@@ -59,6 +59,7 @@ constexpr int RED = W6 + W6_B, RED_B = 8 * ROWS1 * 4;  // compute-wave partials
 constexpr int SM = RED + RED_B, SM_B = 64;             // ok flag, this workgroup's 8 columns of y
 constexpr int TOTAL = SM + SM_B;
 static_assert(TOTAL <= 160 * 1024, "one workgroup per CU");
+static_assert(G == pk::G, "grid waits: 256 arrivals per wait");
 }  // namespace cs
 
 // the four 16-lane rows of a wave summed per lane position (lanes l, l ^ 16, l ^ 32, l ^ 48)
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
   const long long slot = a.slots[0];
   unsigned g0 = 0, nwait = 0;
   if (ctl) __builtin_amdgcn_s_setprio(3);
-  if (ctl) g0 = __hip_atomic_load((hl_gu32*)hl_gen(a.sync), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+  if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_CODEC_STAGE);
   // diagnostics (tools/codec_stage_stamps.py): per block j, slot 8j + k, k =
   // 0 front half begins, 1 fc1 input in LDS, 2 (compute wave 0) fc1 slice landed,
   // 3 fc1 partials in LDS, 4 hidden-row wait released, 5 hidden row in LDS,
@@ -259,9 +260,9 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
     auto grid_wait = [&](auto between) -> bool {
       ++nwait;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) hl_arrive(a.sync, w);
+      if (lane == 0) hl_arrive(a.sync, pk::GEN_CODEC_STAGE, w);
       between();
-      if (lane == 0) ok_s[0] = hl_poll(a.sync, g0, nwait, a.err) ? 1u : 0u;
+      if (lane == 0) ok_s[0] = hl_poll(a.sync, pk::GEN_CODEC_STAGE, g0, pk::SHARDS * nwait, a.err) ? 1u : 0u;
       __syncthreads();
       return ok_s[0] != 0;
     };
@@ -324,9 +325,9 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
         // compute waves to issue it; the poll follows
         ++nwait;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) hl_arrive(a.sync, w);
+        if (lane == 0) hl_arrive(a.sync, pk::GEN_CODEC_STAGE, w);
         __syncthreads();   // B5b
-        if (lane == 0) ok_s[0] = hl_poll(a.sync, g0, nwait, a.err) ? 1u : 0u;
+        if (lane == 0) ok_s[0] = hl_poll(a.sync, pk::GEN_CODEC_STAGE, g0, pk::SHARDS * nwait, a.err) ? 1u : 0u;
         __syncthreads();   // B6
         if (!ok_s[0]) return;
       } else if (!last && !grid_wait([] {})) return;   // B6
@@ -472,6 +473,7 @@ constexpr int NCH = C / 8;                   // 128 chunks per row
 constexpr int CPT = 4;                       // weight chunks per compute thread per GEMV
 constexpr int ROWS1 = F / G, ROWS2 = C / G;  // 16 / 4
 static_assert(ROWS1 * C / 8 == CPT * NTC && ROWS2 * F / 8 == CPT * NTC, "codec stage (C = 1,024) geometry");
+static_assert(G == pk::G, "grid waits: 256 arrivals per wait");
 template <int M>
 struct Lds {
   static constexpr int W1 = 0, W1_B = ROWS1 * C * 2;                          // fc1 slice, 32 KB
@@ -512,7 +514,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
   const long long slot = a.slots[0];
   unsigned g0 = 0, nwait = 0;
   if (ctl) __builtin_amdgcn_s_setprio(3);
-  if (ctl) g0 = __hip_atomic_load((hl_gu32*)hl_gen(a.sync), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+  if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_CODEC_STAGE);
   auto stamp = [&](int k, bool by_ctl) {   // k_codec_stage's slots (tools/codec_stage_stamps.py)
     if (a.stamps && threadIdx.x == (by_ctl ? NTC : 0)) a.stamps[w * 64 + k] = __builtin_amdgcn_s_memrealtime();
   };
@@ -593,9 +595,9 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
     ++nwait;
     if (ctl) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) hl_arrive(a.sync, w);
+      if (lane == 0) hl_arrive(a.sync, pk::GEN_CODEC_STAGE, w);
       between();
-      if (lane == 0) ok_s[0] = hl_poll(a.sync, g0, nwait, a.err) ? 1u : 0u;
+      if (lane == 0) ok_s[0] = hl_poll(a.sync, pk::GEN_CODEC_STAGE, g0, pk::SHARDS * nwait, a.err) ? 1u : 0u;
     }
     __syncthreads();
     return ok_s[0] != 0;

@@ -51,7 +51,7 @@ struct Geo {
   static constexpr int SM = H + H_B, SM_B = 16;
   static constexpr int TOTAL = SM + SM_B;
   static_assert(TOTAL <= 160 * 1024, "LDS");
-  static_assert(C / S == 32 && F / S == HSL, "cluster geometry");
+  static_assert(C / S == 32 && F / S == HSL && S == (int)pk::CW_S[C == 512], "cluster geometry");
 };
 }  // namespace cw
 
@@ -100,26 +100,17 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
       a.stamps[((long long)smp * gridDim.x + blockIdx.x) * 16 + k] = __builtin_amdgcn_s_memrealtime();
   };
   stamp(0);
-  // cluster-wide wait: every wave's write-through stores drained, one arrival,
-  // lane 0 polls (bounded) -> false: gave up (error word set)
+  // cluster-wide wait: every wave's write-through stores drained, one arrival on
+  // the cluster's line of cw_sync (sync_layout.h), lane 0 polls until all S
+  // members made it (persist_dev.h hl_poll, bounded; on (cnt, line 0): through
+  // (a.sync, cluster) the kernel holds 4 more SGPRs) -> false: gave up
   auto cluster_wait = [&]() -> bool {
     ++nwait;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
       __hip_atomic_fetch_add((hl_gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long tw = __builtin_amdgcn_s_memrealtime();
-      unsigned ok = 1;
-      while ((unsigned)(__hip_atomic_load((hl_gu32*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - base) <
-             (unsigned)G::S * nwait) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - tw > 20000000ull) {   // ~200 ms at 100 MHz
-          __hip_atomic_store((hl_gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0;
-          break;
-        }
-      }
-      ok_s[0] = ok;
+      ok_s[0] = hl_poll(cnt, 0, base, (unsigned)G::S * nwait, a.err) ? 1u : 0u;
     }
     __syncthreads();
     return ok_s[0] != 0;

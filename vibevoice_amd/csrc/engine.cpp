@@ -20,6 +20,7 @@
 
 #include "../../include/vibevoice_hip_diag.h"
 #include "kernels.h"
+#include "sync_layout.h"
 
 static thread_local std::string g_err;
 
@@ -87,10 +88,6 @@ static int hl_count(int device) {
   auto it = g_hl_ctxs.find(device);
   return it == g_hl_ctxs.end() ? 0 : it->second;
 }
-
-// wait counters + error word of a grid-waiting kernel family (persist_dev.h: 13 lines of 32 words)
-static constexpr size_t SYNC_BYTES = 2048;
-static constexpr int CW_LINES = 256;   // wide codec stage clusters per C (n x tiles <= 256 by residency)
 
 // Process default for new contexts: VIBEVOICE_PERSISTENT=0 in the environment
 // turns the grid-waiting kernels off (e.g. several processes sharing one GPU).
@@ -191,9 +188,7 @@ struct vv_ctx {
   int head_tp = 0;      // 1: the diffusion head's FFN is sharded too (vv_tp_shard_head; head_ffn is local)
   ncclComm_t comm = nullptr;
   DevBuf zero_rows;     // [2 * max_batch][H] zeros: the residual of a sharded head's rank > 0
-  // grid-wide waits of the one-launch kernels (persist_dev.h): head_m16.hip's
-  // counters (lines 0-7 shards, line 12 its generation) + the error word (line 10)
-  DevBuf hf_sync;
+  DevBuf hf_sync;   // head_m16.hip's wait counters + every grid-waiting kernel's error word (layout: sync_layout.h)
   DevBuf lf_sync;   // lm_ffn.hip's wait counters (+ k_lm_ffn16's column-group tickets)
   DevBuf lf_slab;   // k_lm_ffn16's down partials [48][4][16][32] fp32
   DevBuf la_part;   // k_lm_attn's per-unit attention partials (lm_attn_part_floats)
@@ -227,6 +222,8 @@ struct vv_ctx {
 };
 
 // ------------------------------------------------------------------ helpers
+static std::vector<DevBuf*> sync_bufs(vv_ctx* c) { return {&c->hf_sync, &c->cs_sync, &c->lf_sync}; }   // sync_layout.h's layout
+static unsigned* err_word(vv_ctx* c) { return (unsigned*)c->hf_sync.p + pk::ERR * pk::LINE; }
 static const bf16* W(vv_ctx* c, const std::string& n) {
   auto it = c->w.find(n);
   if (it == c->w.end()) return nullptr;
@@ -650,7 +647,7 @@ static bool codec_wide_any(const ConvNet& net) {
 static bool wide_on(vv_ctx* c, const ConvNet& net, int i, int n) {
   const int C = net.chans[i];
   return g_codec_wide && (C == 256 || C == 512) && persist_on(c) && c->cw_sync.p && !net.mix[i].empty() &&
-         codec_wide_fits(C, net.T[i], n, net.depth[i], net.mix[i][0].ctx) && n * ((net.T[i] + 15) / 16) <= CW_LINES;
+         codec_wide_fits(C, net.T[i], n, net.depth[i], net.mix[i][0].ctx) && n * ((net.T[i] + 15) / 16) <= pk::CW_LINES;
 }
 extern "C" int vv_codec_wide_active(vv_ctx* c, int n) {   // 1: some acoustic-decoder stage runs it now
   if (!c || !c->finalized) return 0;
@@ -798,8 +795,8 @@ static int convnet_run(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap 
       A.out = buf_in_rows(nb, T, slots);
       CHK(c->cw_slab.ensure(codec_wide_slab_floats(C, T, n) * sizeof(float)));
       CHK(c->cw_xbuf.ensure(codec_wide_xbuf_elems(C, T, n) * sizeof(bf16)));
-      A.sync = (unsigned*)c->cw_sync.p + (C == 512 ? CW_LINES * 32 : 0);
-      A.err = (unsigned*)c->hf_sync.p + 10 * 32;
+      A.sync = (unsigned*)c->cw_sync.p + (C == 512 ? pk::CW_HALF : 0);
+      A.err = err_word(c);
       A.slab = (float*)c->cw_slab.p;
       A.xbuf = (bf16*)c->cw_xbuf.p;
       if (unsigned long long* sp = g_codec_wide_stamps.load()) A.stamps = sp + 8192 * (2 * (net.decoder ? 0 : 1) + (C == 512));
@@ -840,7 +837,7 @@ static int convnet_run(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap 
         if (net.mix[i][j].ctx != A.ctx) FAIL("codec stage: conv buffers of one stage differ in history length");
       }
       A.sync = (unsigned*)c->cs_sync.p;
-      A.err = (unsigned*)c->hf_sync.p + 10 * 32;
+      A.err = err_word(c);
       A.stamps = net.decoder && i == g_codec_stage_stamp_at ? g_codec_stage_stamps.load() : nullptr;
       {
         const int v = (g_codec_stage.load() >> 1) & 7;
@@ -1096,9 +1093,11 @@ int vv_finalize(vv_ctx* c) {
     CHK(need(c, p + ".down_w", {H, F}));
   }
   CHK(need(c, "head.final_w", {D, H}));
-  // grid-wait words + the error word (always present: vv_sync_error_async reads it)
-  CHK(c->hf_sync.ensure(SYNC_BYTES));
-  HIPCHK(hipMemset(c->hf_sync.p, 0, SYNC_BYTES));
+  // grid-wait counters + the error word (always present: vv_sync_error_async reads it)
+  for (DevBuf* b : sync_bufs(c)) {
+    CHK(b->ensure(pk::BYTES));
+    HIPCHK(hipMemset(b->p, 0, pk::BYTES));
+  }
   // ---- connectors + latent scaling
   CHK(need(c, "conn.ac.fc1_w", {H, D}));
   CHK(need(c, "conn.se.fc1_w", {H, k.semantic_dim}));
@@ -1128,20 +1127,15 @@ int vv_finalize(vv_ctx* c) {
   }
   CHK(convnet_alloc(c->dec, 7));
   CHK(convnet_alloc(c->sem, 7));
-  // the persistent codec stage's wait counters; a context that can run it (or
-  // the persistent head, or the one-launch head layer at 16 rows) counts in the
-  // device's registry (hl_register)
-  CHK(c->cs_sync.ensure(SYNC_BYTES));
-  HIPCHK(hipMemset(c->cs_sync.p, 0, SYNC_BYTES));
-  CHK(c->lf_sync.ensure(SYNC_BYTES));
-  HIPCHK(hipMemset(c->lf_sync.p, 0, SYNC_BYTES));
+  // a context that can run a grid-waiting kernel (the persistent codec stage, the
+  // one-launch head layer at 16 rows, ...) counts in the device's registry (hl_register)
   if (k.max_batch >= 2 && lm_ffn16_fits(k.hidden, k.intermediate, 16)) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
   const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, LA_MAX_KEYS);
   const bool la_fits = lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
-  CHK(c->cw_sync.ensure(2 * CW_LINES * 128));
-  HIPCHK(hipMemset(c->cw_sync.p, 0, 2 * CW_LINES * 128));
+  CHK(c->cw_sync.ensure(pk::CW_BYTES));
+  HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
   if (c->head_gemv && head_m16_fits(k.hidden, k.head_ffn, 16))
   {
     CHK(c->m16_buf.ensure(16 * 192 * sizeof(float) + 16 * (size_t)k.hidden * sizeof(bf16)));
@@ -1516,7 +1510,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       a.att = P.att;
       a.part = (float*)c->la_part.p;
       a.sync = (unsigned*)c->lf_sync.p;
-      a.err = (unsigned*)c->hf_sync.p + 10 * 32;
+      a.err = err_word(c);
       a.stamps = g_lm_attn_stamps.load();
       a.variant = 7 ^ (g_lm_attn.load() >> 1);
       KCHK(launch_lm_attn(a, P.maxp, st));
@@ -1619,7 +1613,7 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     a.dn = W(c, p + ".down_w");
     a.act = P.act;
     a.sync = (unsigned*)c->lf_sync.p;
-    a.err = (unsigned*)c->hf_sync.p + 10 * 32;
+    a.err = err_word(c);
     a.slab = (float*)c->lf_slab.p;
     a.stamps = g_lm_ffn_stamps.load();
     if (P.ntok <= 2) KCHK(launch_lm_ffn(a, st));
@@ -1775,9 +1769,8 @@ int vv_sync_reset(vv_ctx* c) {
   if (!c->finalized) FAIL("vv_sync_reset before vv_finalize");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipDeviceSynchronize());
-  for (DevBuf* b : {&c->hf_sync, &c->cs_sync, &c->lf_sync})
-    if (b->p) HIPCHK(hipMemset(b->p, 0, SYNC_BYTES));
-  if (c->cw_sync.p) HIPCHK(hipMemset(c->cw_sync.p, 0, c->cw_sync.bytes));
+  for (DevBuf* b : sync_bufs(c)) HIPCHK(hipMemset(b->p, 0, pk::BYTES));   // (allocated by vv_finalize)
+  HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
   HIPCHK(hipDeviceSynchronize());
   return 0;
 }
@@ -1790,7 +1783,7 @@ int vv_sync_error(vv_ctx* c) {
   unsigned v = 0;
   if (c->hf_sync.p) {
     HIPCHK(hipDeviceSynchronize());
-    if (hipMemcpy(&v, (unsigned*)c->hf_sync.p + 10 * 32, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&v, err_word(c), 4, hipMemcpyDeviceToHost) != hipSuccess)
       FAIL("vv_sync_error: reading the error word failed (hipMemcpy)");
     if (v) CHK(vv_sync_reset(c));
   }
@@ -1805,7 +1798,7 @@ int vv_sync_error_async(vv_ctx* c, void* dst, vv_stream vst) {
   hipStream_t st = (hipStream_t)vst;
   if (!dst) FAIL("vv_sync_error_async: dst is NULL");
   if (!c->finalized) FAIL("vv_sync_error_async before vv_finalize");
-  unsigned* word = (unsigned*)c->hf_sync.p + 10 * 32;
+  unsigned* word = err_word(c);
   HIPCHK(hipMemcpyAsync(dst, word, 4, hipMemcpyDefault, st));
   HIPCHK(hipMemsetAsync(word, 0, 4, st));
   return 0;
@@ -1834,38 +1827,45 @@ int vv_set_persistent(vv_ctx* c, int on) {
   return 0;
 }
 int vv_persistent_active(vv_ctx* c) { return c && c->finalized && persist_on(c) ? 1 : 0; }
-// Diagnostic (tests): raise the error word as a grid wait that gave up would.
+// Diagnostic (tests): raise the error word as a grid wait that gave up would, and leave
+// the counters part-advanced as such a launch does: per buffer shard 0 + 5, each
+// generation line + 3, the last ticket + 1; cluster 0 of each cw_sync half + 3.
 extern "C" int vv_diag_raise_sync_error(vv_ctx* c) {
   if (!c->finalized) FAIL("vv_diag_raise_sync_error before vv_finalize");
   HIPCHK(hipDeviceSynchronize());
-  const unsigned one = 1;
-  HIPCHK(hipMemcpy((unsigned*)c->hf_sync.p + 10 * 32, &one, 4, hipMemcpyHostToDevice));
-  // ... and leave the counters part-advanced as a launch that gave up does: 5
-  // arrivals on shard 0, 3 generation bumps (lines 11 and 12) of every family
-  for (DevBuf* b : {&c->hf_sync, &c->cs_sync, &c->lf_sync}) {
-    if (!b->p) continue;
-    for (int line : {0, 11, 12}) {
-      unsigned v = 0;
-      unsigned* p = (unsigned*)b->p + line * 32;
-      HIPCHK(hipMemcpy(&v, p, 4, hipMemcpyDeviceToHost));
-      v += line == 0 ? 5u : 3u;
-      HIPCHK(hipMemcpy(p, &v, 4, hipMemcpyHostToDevice));
-    }
+  auto bump = [](void* buf, int word, unsigned by) -> int {
+    unsigned v = 0, *p = (unsigned*)buf + word;
+    HIPCHK(hipMemcpy(&v, p, 4, hipMemcpyDeviceToHost));
+    v += by;
+    HIPCHK(hipMemcpy(p, &v, 4, hipMemcpyHostToDevice));
+    return 0;
+  };
+  CHK(bump(c->hf_sync.p, pk::ERR * pk::LINE, 1));
+  for (DevBuf* b : sync_bufs(c)) {
+    CHK(bump(b->p, 0, 5));
+    for (int line : pk::GEN_LINES) CHK(bump(b->p, line * pk::LINE, 3));
+    CHK(bump(b->p, pk::TICKET0 + pk::TICKETS - 1, 1));
   }
+  for (int half = 0; half < 2; ++half) CHK(bump(c->cw_sync.p, half * pk::CW_HALF, 3));
   return 0;
 }
-// Diagnostic (tests): word 0 of the 13 counter lines of each wait family
-// (head, codec stage, LM MLP) -> out[39].  Between launches a consistent set has
-// every shard line (0-7) a multiple of 32 and every generation line a multiple of 8.
-extern "C" int vv_diag_sync_words(vv_ctx* c, unsigned* out) {
-  if (!c->finalized) FAIL("vv_diag_sync_words before vv_finalize");
+// Diagnostic (tests): the counters between launches -> out[n >= pk::DIAG_WORDS] (vibevoice_hip_diag.h)
+extern "C" int vv_diag_sync_words(vv_ctx* c, unsigned* out, int n) {
+  if (!c->finalized || n < pk::DIAG_WORDS) FAIL("vv_diag_sync_words before vv_finalize, or out[] shorter than 53 words");
   HIPCHK(hipDeviceSynchronize());
-  int i = 0;
-  for (DevBuf* b : {&c->hf_sync, &c->cs_sync, &c->lf_sync})
-    for (int line = 0; line < 13; ++line, ++i) {
-      out[i] = 0;
-      if (b->p) HIPCHK(hipMemcpy(out + i, (unsigned*)b->p + line * 32, 4, hipMemcpyDeviceToHost));
-    }
+  std::vector<unsigned> h(2 * pk::CW_HALF);
+  auto max_mod = [&](int w0, int n, int stride, unsigned m) {   // the highest residue of n counters
+    unsigned r = 0;
+    for (int i = 0; i < n; ++i) r = std::max(r, h[w0 + i * stride] % m);
+    return r;
+  };
+  for (DevBuf* b : sync_bufs(c)) {
+    HIPCHK(hipMemcpy(h.data(), b->p, pk::BYTES, hipMemcpyDeviceToHost));
+    for (int line = 0; line < pk::LINES; ++line) *out++ = h[line * pk::LINE];
+    *out++ = max_mod(pk::TICKET0, pk::TICKETS, 1, pk::TICKET_STEP);
+  }
+  HIPCHK(hipMemcpy(h.data(), c->cw_sync.p, pk::CW_BYTES, hipMemcpyDeviceToHost));
+  for (int half = 0; half < 2; ++half) *out++ = max_mod(half * pk::CW_HALF, pk::CW_LINES, pk::LINE, pk::CW_S[half]);
   return 0;
 }
 
@@ -2031,7 +2031,7 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
     a.dn = W(c, p + ".down_w");
     a.act = h.act;
     a.sync = (unsigned*)c->hf_sync.p;
-    a.err = (unsigned*)c->hf_sync.p + 10 * 32;
+    a.err = err_word(c);
     a.stamps = g_head_m16_stamps;
     // the A side ahead of every weight load: at 16 rows (B = 8) a whole head
     // sample 890 -> 860 us, at 2 rows (B = 1) 595 -> 603 us (tools/head_m16_stamps.py)

@@ -54,6 +54,7 @@ constexpr int ACT = 0, RED2 = (SM + SM_B + 15) / 16 * 16;
 constexpr int TOTAL = RED2 + 8 * 256 * 4;
 static_assert(TOTAL <= 160 * 1024 && 3 * 8 * 256 * 4 <= RMAX * H * 2, "head m16 LDS");
 static_assert(ACT + RMAX * AST * 2 <= SM, "the act rows stay clear of the small region");
+static_assert(G == pk::G, "grid waits: 256 arrivals per wait");
 }  // namespace hm
 
 __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
@@ -97,7 +98,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
   };
   stamp(0, true);
   if (ctl) __builtin_amdgcn_s_setprio(3);
-  if (ctl) g0 = __hip_atomic_load((hl_gu32*)(a.sync + 12 * pk::LINE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+  if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_HEAD_M16);
 
   bf16x8 wb[WB];
   // this workgroup's half down tile into the registers (in flight through the
@@ -201,7 +202,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    if (ctl && lane == 0) ok_s[1] = hl_grid_wait_gen(a.sync, 12, g0, 1, w, a.err) ? 1u : 0u;
+    if (ctl && lane == 0) ok_s[1] = hl_grid_wait(a.sync, pk::GEN_HEAD_M16, g0, 1, w, a.err) ? 1u : 0u;
     __syncthreads();
     stamp(2, true);
     if (!ok_s[1]) return;
@@ -292,7 +293,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
                  *(const bf16x4*)(su_s + (j * RMAX + m) * 8 + 4 * half));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) ok_s[0] = hl_grid_wait_gen(a.sync, 12, g0, a.pre ? 2 : 1, w, a.err) ? 1u : 0u;
+    if (lane == 0) ok_s[0] = hl_grid_wait(a.sync, pk::GEN_HEAD_M16, g0, a.pre ? 2 : 1, w, a.err) ? 1u : 0u;
   }
   __syncthreads();
   stamp(6, true);

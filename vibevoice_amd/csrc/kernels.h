@@ -210,8 +210,9 @@ struct SumRows {
 };
 
 
-// ---- the one-launch kernels with grid-wide waits (persist_dev.h): k_head_m16,
-// k_lm_ffn, k_codec_stage*.  Residency rule: every workgroup of the grid must be
+// ---- the one-launch kernels with grid-wide waits (persist_dev.h; counters:
+// sync_layout.h): k_head_m16, k_lm_ffn, k_lm_ffn16, k_lm_attn, k_codec_stage,
+// k_codec_stage_s, k_codec_wide.  Residency rule: every workgroup of the grid must be
 // resident at once -- the occupancy query's blocks per CU times the device's CUs
 // covers the grid, and no scratch (a wave waiting for a scratch slot is not
 // resident).  The engine also requires the context to be the device's only
@@ -235,7 +236,7 @@ struct HeadM16Args {
   const bf16* gu;           // gate|up, MFMA-packed [2F][H] (EPI_SILU_MUL pairing)
   const bf16* dn;           // down, MFMA-packed [H][F]
   bf16* act;                // [16][F] SiLU(gate) * up rows (workspace, written through)
-  unsigned* sync;           // the head's wait lines: shards 0-7, this kernel's generation at line 12
+  unsigned* sync;           // hf_sync (sync_layout.h: shard lines, generation pk::GEN_HEAD_M16)
   unsigned* err;            // set to 1 when the grid wait gave up
   unsigned long long* stamps;   // diagnostics (tools/head_m16_stamps.py): [G][16] s_memrealtime, or nullptr
   int a_first;              // 1: every wave's A-side DMA issued before any weight load (a barrier between)
@@ -296,8 +297,8 @@ struct LmFfnArgs {
   const bf16* gu;    // gate|up [2F][H], MFMA-packed (8 gate + 8 up rows per tile)
   const bf16* dn;    // down [H][F], MFMA-packed
   bf16* act;         // [R][F] SiLU(gate) * up, the hand-off rows
-  unsigned* sync;    // shards 0-7, generation at line 11 (k_lm_ffn) / 12 (k_lm_ffn16); k_lm_ffn16's
-                     // column-group tickets at word 13 x 32
+  unsigned* sync;    // lf_sync (sync_layout.h: shard lines, generation pk::GEN_LM_FFN / GEN_LM_FFN16,
+                     // k_lm_ffn16's column-group tickets from word pk::TICKET0)
   unsigned* err;     // set to 1 when the grid wait gave up
   float* slab;       // k_lm_ffn16: [48 column groups][4 hidden ranges][16][32] fp32 partials of down
   unsigned long long* stamps;   // diagnostics: [256][16] s_memrealtime per phase, or nullptr
@@ -322,7 +323,7 @@ struct LmAttnArgs {
   RowMap res, out;   // residual rows (read) and output rows (written): x + o_proj(attention)
   bf16* att;         // [R][H] merged attention rows (the o_proj hand-off, written through)
   float* part;       // [units][6 * 128 + 12] per-unit (O, m, l) partials
-  unsigned* sync;    // shards 0-7, this kernel's generation at line 15
+  unsigned* sync;    // lf_sync (sync_layout.h: shard lines, generation pk::GEN_LM_ATTN)
   unsigned* err;     // set to 1 when a grid wait gave up
   unsigned long long* stamps;   // diagnostics: [256][16] s_memrealtime per phase, or nullptr
   int variant;              // bits (all set by default; vv_lm_attn bits 1..3 clear them, A/B): 1 = A
@@ -352,7 +353,7 @@ struct CodecStageArgs {
   bf16* h;                  // [M][4C] hidden rows (written through)
   RowMap out;               // the last block's output rows
   CodecStageBlock b[8];
-  unsigned* sync;           // 12 lines of 32 words (shards 0-7, generation 11)
+  unsigned* sync;           // cs_sync (sync_layout.h: shard lines, generation pk::GEN_CODEC_STAGE)
   unsigned* err;            // set to 1 when a grid wait gave up
   unsigned long long* stamps;   // diagnostics: [G][64] s_memrealtime per phase, or nullptr
   int pubfirst;             // C = 2,048 weight-stream issue (codec_stage.hip): 0 = a block's whole
@@ -406,7 +407,7 @@ struct CodecWideArgs {
   const bf16* x;            // stage input rows [n][T][C]
   CodecTileBlock b[3];
   RowMap out;               // stage output rows (row = sample * T + t)
-  unsigned* sync;           // one 32-word line per cluster (n x tiles), monotonic counters
+  unsigned* sync;           // this C's half of cw_sync (sync_layout.h): one line per cluster (n x tiles), monotonic counters
   unsigned* err;            // set to 1 when a wait gave up
   float* slab;              // [n x tiles][S][40][C] fp32 partials
   bf16* xbuf;               // [n x tiles][40][C] block outputs

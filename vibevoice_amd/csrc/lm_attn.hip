@@ -26,7 +26,7 @@
 //   4. the o_proj workgroups DMA the attention rows, MFMA with the resident
 //      weights, residual epilogue.
 // Hand-offs: write-through (sc1) stores, each storing wave's vmcnt(0), a
-// workgroup barrier, lane 0's arrival (persist_dev.h hl_grid_wait_gen); readers
+// workgroup barrier, lane 0's arrival (persist_dev.h hl_grid_wait); readers
 // use sc1 / nt loads (L1-bypassing; MI355X_MICROARCH.md's hand-off table, first
 // row).  Arithmetic: epi_rope's and k_attn's (scores scaled after the MFMA, P
 // rounded to bf16 for P.V, l in fp32), the units merged as k_attn merges splits.
@@ -47,8 +47,8 @@ constexpr int SM = NWS + NWS_B, SM_B = 64 + 4 * (2 * RMAX + 1) + 12;
 // 82 KB: one workgroup per CU (two would share a CU while another idles)
 constexpr int TOTAL = (SM + SM_B) > 82 * 1024 ? (SM + SM_B) : 82 * 1024;
 constexpr int PART = G * D + 2 * G;              // floats per unit partial: O[6][128], then (m, l) x 6
-constexpr int GEN = 15;                          // this kernel's generation line in the sync buffer
 static_assert(SM + SM_B <= 160 * 1024, "lm attn LDS");
+static_assert(GRID == pk::G, "grid waits: 256 arrivals per wait");
 }  // namespace la
 
 DEV void la_stamp(const LmAttnArgs& a, int k) {
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   const bool qt = w < TQ, ot = w >= O0 && w < O0 + TO;
   unsigned g0 = 0;
   if (threadIdx.x == 0)
-    g0 = __hip_atomic_load((hl_gu32*)(a.sync + GEN * pk::LINE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+    g0 = hl_base_gen(a.sync, pk::GEN_LM_ATTN);
   // the attention units: pair p = row * NKV + kv head holds ceil(len / 32) of
   // them (positions read first: a wait for them then leaves the streams in flight)
   int nunit = 0;
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   }
   la_stamp(a, 2);
   __syncthreads();
-  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait_gen(a.sync, GEN, g0, 1, w, a.err) ? 1u : 0u;
+  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait(a.sync, pk::GEN_LM_ATTN, g0, 1, w, a.err) ? 1u : 0u;
   __syncthreads();
   la_stamp(a, 3);
   if (!ok_s[0]) return;
@@ -349,7 +349,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   la_stamp(a, 4);
   __syncthreads();
-  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait_gen(a.sync, GEN, g0, 2, w, a.err) ? 1u : 0u;
+  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait(a.sync, pk::GEN_LM_ATTN, g0, 2, w, a.err) ? 1u : 0u;
   __syncthreads();
   la_stamp(a, 5);
   if (!ok_s[0]) return;
@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   la_stamp(a, 6);
   __syncthreads();
-  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait_gen(a.sync, GEN, g0, 3, w, a.err) ? 1u : 0u;
+  if (threadIdx.x == 0) ok_s[0] = hl_grid_wait(a.sync, pk::GEN_LM_ATTN, g0, 3, w, a.err) ? 1u : 0u;
   __syncthreads();
   la_stamp(a, 7);
   if (!ok_s[0] || !ot) return;

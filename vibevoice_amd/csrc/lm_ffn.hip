@@ -45,6 +45,7 @@ constexpr int DN2 = WT, RED2 = WT + 8 * SLOT2 * 512;        // phase B: down blo
 static_assert(TOTAL <= 160 * 1024 && XS_B % 16 == 0 && NW % 16 == 0 && WT % 16 == 0, "lm ffn LDS");
 static_assert(RMAX * AST * 2 <= RED1_B && RED2 + 8 * 256 * 4 <= WT + WT_B, "lm ffn phase-B LDS");
 static_assert(4 * 4 + RMAX * 4 + 6 * RMAX * 8 * 2 + RMAX * 8 * 2 <= SM_B, "lm ffn small region");
+static_assert(G == pk::G, "grid waits: 256 arrivals per wait");
 }  // namespace lf
 
 __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
@@ -83,7 +84,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
   const int col0 = 8 * d;
   unsigned g0 = 0;
   if (ctl) __builtin_amdgcn_s_setprio(3);
-  if (ctl) g0 = __hip_atomic_load((hl_gu32*)(a.sync + 11 * pk::LINE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+  if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_LM_FFN);
   // diagnostics (k_lm_ffn16's numbering): 0 start, 1 A side in LDS, 2 normalised, 3 gate|up
   // products, 4 SiLU * up, 5 hand-off released, 6 act rows + down weights landed, 9 end
   auto stamp = [&](int k) {
@@ -220,7 +221,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
                  *(const bf16x4*)(su_s + (j * RMAX + m) * 8 + 4 * half));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) ok_s[0] = hl_grid_wait_gen(a.sync, 11, g0, 1, w, a.err) ? 1u : 0u;
+    if (lane == 0) ok_s[0] = hl_grid_wait(a.sync, pk::GEN_LM_FFN, g0, 1, w, a.err) ? 1u : 0u;
   }
   __syncthreads();
   stamp(5);
@@ -320,8 +321,9 @@ constexpr int RED = NW + NW_B, RED_B = 6 * 2 * 256 * 4;  // [6 tiles][2 halves] 
 constexpr int SU = RED + RED_B, SU_B = 6 * RMAX * 8 * 2;
 constexpr int SM = SU + SU_B, SM_B = 128;                // ok, last, inv[16]
 constexpr int TOTAL = SM + SM_B;
-constexpr int TK = 13 * pk::LINE;                        // ticket words in the sync buffer (after the 13 counter lines)
 static_assert(RMAX * XST * 2 <= XS_B && TOTAL <= 160 * 1024, "lm ffn16 LDS");
+static_assert(G == pk::G && NG == pk::TICKETS && NR == pk::TICKET_STEP,
+              "grid waits: 256 arrivals per wait; one ticket word per column group, one arrival per hidden range");
 }  // namespace lf16
 
 __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
@@ -347,7 +349,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   const int grp = w >> 2, rng = w & 3;                             // down: columns [32 grp, +32), k-blocks [70 rng, +70)
   unsigned g0 = 0;
   if (ctl) __builtin_amdgcn_s_setprio(3);
-  if (ctl) g0 = __hip_atomic_load((hl_gu32*)(a.sync + 12 * pk::LINE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~7u;
+  if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_LM_FFN16);
   // diagnostics: 0 start, 1 A side in LDS, 2 A side normalised, 3 gate|up products, 4 SiLU * up,
   // 5 hand-off released, 6 act rows + down weights landed, 7 down products, 8 partial published, 9 end
   auto stamp = [&](int k) {
@@ -428,7 +430,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
                    *(const bf16x4*)(su_s + (j * RMAX + m) * 8 + 4 * half));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) hl_arrive_gen(a.sync, 12, w);
+    if (lane == 0) hl_arrive(a.sync, pk::GEN_LM_FFN16, w);
   }
   __syncthreads();
   if (wave < 10 && owner) {
@@ -441,7 +443,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
 #pragma unroll
     for (int kk = 0; kk < KW2; ++kk) wb[kk] = hl_ldnt(dw + (long long)kk * 512);
   }
-  if (ctl && lane == 0) ok_s[0] = hl_poll_gen(a.sync, 12, g0, 1, a.err) ? 1u : 0u;
+  if (ctl && lane == 0) ok_s[0] = hl_poll(a.sync, pk::GEN_LM_FFN16, g0, pk::SHARDS, a.err) ? 1u : 0u;
   __syncthreads();
   stamp(5);
   if (!ok_s[0] || !owner) return;
@@ -481,7 +483,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned t = __hip_atomic_fetch_add((hl_gu32*)(a.sync + TK + grp), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned t = __hip_atomic_fetch_add((hl_gu32*)(a.sync + pk::TICKET0 + grp), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ok_s[1] = (t & 3) == 3 ? 1u : 0u;   // the group's 4th arrival of this launch sums it
   }
   __syncthreads();

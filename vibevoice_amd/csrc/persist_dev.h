@@ -1,15 +1,12 @@
-// Device helpers of the persistent kernels (head_loop.hip, codec_stage.hip): one
-// workgroup per CU (G = 256), a control wave doing the hand-offs, grid-wide waits
-// on XCD-sharded counters.
+// Device helpers of the grid-waiting kernels (head_m16.hip, lm_ffn.hip,
+// lm_attn.hip, codec_stage.hip, codec_wide.hip): one workgroup per CU (G = 256),
+// a control wave doing the hand-offs, grid-wide waits on XCD-sharded counters
+// (sync_layout.h: which counter lives where).
 #pragma once
 #include "gemv_dev.h"
+#include "sync_layout.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"
-
-namespace pk {
-constexpr int G = 256;              // workgroups of a persistent launch (one per CU)
-constexpr int LINE = 32;            // words per counter line
-}  // namespace pk
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const bf16x8 hl_gbf16x8;
@@ -67,39 +64,44 @@ DEV const bf16* hl_packed(const bf16* w, int K, int j, int k) {
 }
 
 // One grid-wide wait: arrival of this workgroup + poll until k waits of this
-// launch have completed.  Control wave, lane 0, behind the control wave's own
-// s_waitcnt vmcnt(0) (it made every store this workgroup publishes).  The
+// launch have completed.  Lane 0 of the control wave (or of the wave that made
+// the workgroup's last store), behind that wave's own s_waitcnt vmcnt(0).  The
 // arrival adds to this workgroup's XCD shard counter (w % 8: 32 workgroups
-// each); a shard's 32nd arrival of a wait bumps this kernel's generation word,
+// each); a shard's 32nd arrival of a wait bumps the kernel's generation word at
+// `line` (sync_layout.h: only that kernel bumps it; the shard lines are shared),
 // so one wait completes when the generation has advanced by 8.  Two chained
-// device-scope atomics before the release (round 4's k_head_ffn chained three:
-// shard -> top -> generation).  Measured against (DESIGN.md "Persistent head"):
-// polling all 256 per-workgroup flags (2x slower: 256 pollers sweeping the same
-// lines) and polling the 8 shard counters without the generation word (one
-// atomic per wait, but 8 lines per poll: 755 -> 774 us per head sample).
-// Counters are monotonic across launches and compared wrap-safe.
+// device-scope atomics before the release.  Measured against (DESIGN.md
+// "Persistent head"): polling all 256 per-workgroup flags (2x slower: 256
+// pollers sweeping the same lines) and polling the 8 shard counters without the
+// generation word (one atomic per wait, but 8 lines per poll: 755 -> 774 us per
+// head sample).  Counters are monotonic across launches and compared wrap-safe.
 //
-// The launch's base generation: only this kernel bumps its word (line 11; the
-// shard counters are shared with k_head_ffn, 256 workgroups and 32 arrivals per
-// shard per wait in both), 8 per wait, so it is a multiple of 8 between
-// launches.  A workgroup reading it at entry may see up to 7 bumps of the first
-// wait (other shards complete it; its own cannot): base = word rounded down to 8.
-DEV unsigned* hl_gen(unsigned* sync) { return sync + 11 * pk::LINE; }
-
-// arrival of workgroup w (lane 0 of the control wave)
-DEV void hl_arrive(unsigned* sync, int w) {
-  using namespace pk;
-  const unsigned v = __hip_atomic_fetch_add((hl_gu32*)(sync + (w & 7) * LINE), 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-  if ((v + 1) % (G / 8) == 0) __hip_atomic_fetch_add((hl_gu32*)hl_gen(sync), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The launch's base generation, read at entry: the word moves 8 per wait, so it
+// is a multiple of 8 between launches.  A workgroup reading it at entry may see
+// up to 7 bumps of the first wait (other shards complete it; its own cannot):
+// base = word rounded down to 8.
+DEV unsigned hl_base_gen(unsigned* sync, int line) {
+  return __hip_atomic_load((hl_gu32*)(sync + line * pk::LINE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+         ~(unsigned)(pk::SHARDS - 1);
 }
-// poll the generation word until it has advanced by 8 k from g0; false: gave up
-// after ~200 ms (error word set).  (A/B builds, tools/ab_lib.sh: two polls in
-// flight half a round trip apart, or s_sleep 4 between polls: B = 1 within
-// +-0.01 ms of this one-at-a-time loop.)
-DEV bool hl_poll_word(unsigned* gen, unsigned g0, unsigned k, unsigned* err) {
+// arrival of workgroup w
+DEV void hl_arrive(unsigned* sync, int line, int w) {
+  using namespace pk;
+  const unsigned v = __hip_atomic_fetch_add((hl_gu32*)(sync + (w & (SHARDS - 1)) * LINE), 1u, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+  if ((v + 1) % (G / SHARDS) == 0)
+    __hip_atomic_fetch_add((hl_gu32*)(sync + line * LINE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// poll word 0 of `line` until it has advanced by `adv` from g0 (k grid waits:
+// adv = SHARDS * k); false: gave up after ~200 ms (error word set).  (A/B builds,
+// tools/ab_lib.sh: two polls in flight half a round trip apart, or s_sleep 4
+// between polls: B = 1 within +-0.01 ms of this one-at-a-time loop.  Polling by
+// scalar loads that miss the scalar cache was tried: the hand-offs took 11-20 us
+// instead of 1.4-3.)
+DEV bool hl_poll(unsigned* sync, int line, unsigned g0, unsigned adv, unsigned* err) {
+  hl_gu32* word = (hl_gu32*)(sync + line * pk::LINE);
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  while ((unsigned)(__hip_atomic_load((hl_gu32*)gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - g0) < 8 * k) {
+  while ((unsigned)(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - g0) < adv) {
     __builtin_amdgcn_s_sleep(1);
     if (__builtin_amdgcn_s_memrealtime() - t0 > 20000000ull) {   // ~200 ms at 100 MHz
       __hip_atomic_store((hl_gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -108,38 +110,8 @@ DEV bool hl_poll_word(unsigned* gen, unsigned g0, unsigned k, unsigned* err) {
   }
   return true;
 }
-// poll until k waits of this launch (base generation g0) have completed; false:
-// gave up after ~200 ms (error word set)
-DEV bool hl_poll(unsigned* sync, unsigned g0, unsigned k, unsigned* err) {
-  return hl_poll_word(hl_gen(sync), g0, k, err);
-}
-DEV bool hl_grid_wait(unsigned* sync, unsigned g0, unsigned k, int w, unsigned* err) {
-  hl_arrive(sync, w);
-  return hl_poll(sync, g0, k, err);
-}
-
-// the arrival half of hl_grid_wait_gen (lane 0 of a wave, behind that wave's vmcnt(0))
-DEV void hl_arrive_gen(unsigned* sync, int gen_line, int w) {
-  using namespace pk;
-  const unsigned v = __hip_atomic_fetch_add((hl_gu32*)(sync + (w & 7) * LINE), 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-  if ((v + 1) % (G / 8) == 0)
-    __hip_atomic_fetch_add((hl_gu32*)(sync + gen_line * LINE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the poll half: until k waits of this launch (base g0) completed; false: gave up
-// after ~200 ms (error word set).  (Polling by scalar loads that miss the scalar
-// cache was tried: the hand-offs took 11-20 us instead of 1.4-3.)
-DEV bool hl_poll_gen(unsigned* sync, int gen_line, unsigned g0, unsigned k, unsigned* err) {
-  return hl_poll_word(sync + gen_line * pk::LINE, g0, k, err);
-}
-
-// the same wait on the generation word at line `gen_line` of `sync` (a kernel of
-// its own: only it bumps that word, 8 per wait; the shard lines are shared)
-DEV bool hl_grid_wait_gen(unsigned* sync, int gen_line, unsigned g0, unsigned k, int w, unsigned* err) {
-  using namespace pk;
-  unsigned* gen = sync + gen_line * LINE;
-  const unsigned v = __hip_atomic_fetch_add((hl_gu32*)(sync + (w & 7) * LINE), 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-  if ((v + 1) % (G / 8) == 0) __hip_atomic_fetch_add((hl_gu32*)gen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return hl_poll_word(gen, g0, k, err);
+// arrive + poll until k waits of this launch (base generation g0) have completed
+DEV bool hl_grid_wait(unsigned* sync, int line, unsigned g0, unsigned k, int w, unsigned* err) {
+  hl_arrive(sync, line, w);
+  return hl_poll(sync, line, g0, pk::SHARDS * k, err);
 }
