@@ -79,9 +79,12 @@ int vv_create(const vv_config* cfg, int device, vv_ctx** out);
 void vv_destroy(vv_ctx* ctx);
 
 /* Borrow a device weight under an engine name (see vibevoice_amd/weights.py
- * for the name list and the packing applied to the reference's tensors). */
+ * for the name list and the packing applied to the reference's tensors).
+ * Before vv_finalize only: afterwards it fails ("after vv_finalize"). */
 int vv_bind_weight(vv_ctx* ctx, const char* name, const void* dev_ptr, const int64_t* shape, int ndim);
-/* Check every required weight is bound; allocate KV / codec state / workspaces. */
+/* Check every required weight is bound with its shape and resolve its pointer
+ * ("missing weight: <name>", "shape mismatch for <name>"); allocate KV / codec
+ * state / workspaces. */
 int vv_finalize(vv_ctx* ctx);
 /* FP8 (OCP e4m3fn) weight-only storage of the LM projections is signalled by
  * which weights are bound: each of lm.<l>.qkv_w / o_w / gu_w / down_w is bound

@@ -14,6 +14,7 @@
 """
 import json
 import os
+import re
 
 import pytest
 import torch
@@ -187,6 +188,66 @@ def test_grid_wait_error_on_the_last_step_without_streamer():
     assert torch.equal(clean.sequences, again.sequences)
     for b in range(2):
         assert torch.equal(clean.speech_outputs[b].cpu(), again.speech_outputs[b].cpu())
+
+
+@pytest.fixture(scope="module")
+def tiny_packed():
+    """The tiny config and its packed engine weights (device tensors), packed once."""
+    from vibevoice_amd.weights import pack
+    cfg = tiny_config()
+    sd = synthetic_state_dict(cfg, seed=13, device="cpu", mode="test", with_acoustic_encoder=False)
+    with torch.cuda.device(dev):
+        return cfg, pack(sd, cfg, torch.device(dev), with_acoustic_encoder=False)
+
+
+@pytest.mark.parametrize("name", ["dec.s0.b0.norm", "dec.s0.b0.ffn_norm", "sem.s0.b0.norm", "lm.0.post_norm",
+                                  "head.0.norm"])
+def test_finalize_names_a_missing_weight(tiny_packed, name):
+    """vv_finalize resolves every weight a kernel reads in the statement that checks
+    it, so an engine that lacks one fails at construction with the name -- also for
+    the Block1D norms, which every codec path reads.  No kernel is launched."""
+    from vibevoice_amd.engine import Engine
+    cfg, w = tiny_packed
+    assert name in w
+    with pytest.raises(RuntimeError, match="missing weight: " + re.escape(name) + "$"):
+        Engine(cfg, None, dev, max_batch=1, max_ctx=64, packed={k: v for k, v in w.items() if k != name})
+
+
+def test_finalize_checks_block_norm_shape(tiny_packed):
+    from vibevoice_amd.engine import Engine
+    cfg, w = tiny_packed
+    C = w["dec.s0.b0.norm"].shape[0]
+    bad = dict(w)
+    bad["dec.s0.b0.norm"] = torch.ones(C + 1, dtype=torch.bfloat16, device=dev)
+    with pytest.raises(RuntimeError, match=re.escape("shape mismatch for dec.s0.b0.norm")):
+        Engine(cfg, None, dev, max_batch=1, max_ctx=64, packed=bad)
+
+
+def test_bind_weight_after_finalize_is_rejected():
+    """A finalized engine's weight table is resolved (and captured graphs hold its
+    pointers): a late vv_bind_weight fails, and the engine generates what it did."""
+    import ctypes
+    from vibevoice_amd import _lib
+    cfg = tiny_config()
+    sd = synthetic_state_dict(cfg, seed=13, device="cpu", mode="test", with_acoustic_encoder=False)
+    m = VibeVoiceForConditionalGenerationInference(cfg, sd, dev, max_batch=1, max_ctx=64)
+    m.set_ddpm_inference_steps(2)
+    ids = torch.randint(0, 151000, (1, 12), generator=torch.Generator().manual_seed(4))
+
+    def step():
+        torch.manual_seed(5)
+        out = m.generate(input_ids=ids, attention_mask=torch.ones_like(ids), tokenizer=TOK, cfg_scale=1.3,
+                         forced_tokens=[[D, X]], show_progress_bar=False)
+        return out.speech_outputs[0].cpu()
+    before = step()
+    L = _lib.lib()
+    for name in ("dec.s0.b0.norm", "head.0.norm"):
+        other = torch.zeros_like(m.engine.w[name])
+        shape = (ctypes.c_int64 * 1)(*other.shape)
+        assert L.vv_bind_weight(m.engine.h, name.encode(), ctypes.c_void_p(other.data_ptr()), shape, 1) != 0
+        assert b"after vv_finalize" in L.vv_last_error()
+    after = step()
+    assert before.numel() == m.engine.hop and torch.equal(after, before)
 
 
 def test_noise_scheduler_swap_sde():

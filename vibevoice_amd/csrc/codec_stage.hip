@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
   bf16x8 xv[4], nw[4], db[4], gm[4], fw[4];
   auto front_load = [&](int j) {
     const int lane = hl_vopaque((int)threadIdx.x & 63);
-    const CodecStageBlock& B = a.b[j];
+    const Block1D& B = a.b[j];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int c = lane + 64 * q;
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
   };
   auto front = [&](int j) {
     const int lane = hl_vopaque((int)threadIdx.x & 63);
-    const CodecStageBlock& B = a.b[j];
+    const Block1D& B = a.b[j];
     float ss = 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {   // per-chunk sums, then chunks in ascending order (XF_MIX's)

@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
   const int nt2 = G::NT2 >= NW ? wave : wave % G::NT2;          // fc2: one tile, row tiles strided by RS
   const int rs2 = G::NT2 >= NW ? 0 : wave / G::NT2;
   auto load_aux = [&](int j, Aux& x) {
-    const CodecTileBlock& b = a.b[j];
+    const Block1D& b = a.b[j];
     x.wn = *(const bf16x8*)(b.norm + c2 * 8);
     x.bb = *(const bf16x8*)(b.dw_b + c2 * 8);
     x.gv = *(const bf16x8*)(b.gamma + c2 * 8);
@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
   // ---------------------------------------------------------------- the blocks
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const CodecTileBlock& bj = a.b[j];
+    const Block1D& bj = a.b[j];
     const int lo = max(0, L0 + 6 * (j + 1));   // first output row of block j
     const int cs = lo - 6;                       // first conv input row
     // ---- M1: conv input rows = norm(x) (history rows t < 0 from the buffer)

@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
   const int nu = s * G::HSL + wave * 16;        // this wave's fc1 tile: hidden units nu .. nu + 15
   const int rcol = s * 32 + 4 * (tid & 7);      // reduce-scatter: this thread's 4 output columns
   auto load_aux = [&](int j, Aux& x) {
-    const CodecTileBlock& b = a.b[j];
+    const Block1D& b = a.b[j];
     x.wn = *(const bf16x8*)(b.norm + c2 * 8);
     x.bb = *(const bf16x8*)(b.dw_b + c2 * 8);
     x.gv = *(const bf16x8*)(b.gamma + c2 * 8);
@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    const CodecTileBlock& bj = a.b[j];
+    const Block1D& bj = a.b[j];
     const int lo = max(0, L0 + 6 * (j + 1));
     const int cs = lo - 6;
     // ---- M1: conv input rows = norm(x) (history rows t < 0 from the buffer)

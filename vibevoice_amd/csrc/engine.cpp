@@ -142,7 +142,27 @@ struct ConvNet {
   bf16* F = nullptr;
   std::vector<RollDesc> rolls;
   DevBuf d_rolls;
+  // weights, resolved by convnet_check (vv_finalize); tr_w[i] / tr_b[i]: the transition before stage i
+  const bf16 *stem_w = nullptr, *stem_b = nullptr, *head_w = nullptr, *head_b = nullptr;
+  const bf16 *tr_w[VV_MAX_STAGES] = {}, *tr_b[VV_MAX_STAGES] = {};
+  std::vector<std::vector<Block1D>> blk;   // [stage][block]: weights + the conv buffer mix[stage][block] (convnet_alloc)
 };
+
+// An LM projection's weight operand: the bf16 matrix, or the FP8 codes + row exponents
+struct LmW {
+  const bf16* w = nullptr;
+  const unsigned char* w8 = nullptr;
+  const signed char* w8e = nullptr;
+};
+// The resolved weight table (vv_ctx: lm, lmw, head, headw, conn_ac, conn_se, scaling;
+// ConvNet: stem, head, tr, blk): vv_finalize fills each entry in the need() call that
+// checks the name's presence and shape, and every later call reads the table only
+struct LmLayerW {
+  const bf16 *in_norm = nullptr, *qkv_b = nullptr, *post_norm = nullptr;
+  LmW qkv, o, gu, down;
+};
+struct HeadLayerW { const bf16 *norm = nullptr, *gu = nullptr, *down = nullptr; };
+struct ConnW { const bf16 *fc1_w = nullptr, *fc1_b = nullptr, *norm = nullptr, *fc2_w = nullptr, *fc2_b = nullptr; };
 
 }  // namespace
 
@@ -156,8 +176,21 @@ extern "C" int vv_attn_stamps(void* buf) {
 struct vv_ctx {
   vv_config cfg;
   int device = 0;
-  std::unordered_map<std::string, Weight> w;
+  std::unordered_map<std::string, Weight> w;   // vv_bind_weight -> vv_finalize only
   bool finalized = false;
+  // the resolved weights (vv_finalize)
+  struct {
+    const bf16 *embed = nullptr, *lm_head = nullptr, *norm = nullptr;
+    const float* inv_freq = nullptr;
+  } lm;
+  std::vector<LmLayerW> lmw;
+  struct {
+    const bf16 *noisy = nullptr, *cond = nullptr, *t0 = nullptr, *t2 = nullptr, *ada = nullptr, *final = nullptr;
+  } head;
+  std::vector<HeadLayerW> headw;
+  ConnW conn_ac, conn_se;
+  const bf16 *scaling = nullptr, *bias = nullptr;   // speech_scaling_factor, speech_bias_factor
+  bool has_aenc = false;                            // the optional acoustic encoder (aenc.*) is bound
   // LM
   int qkv_n = 0, lm_slots = 0;
   DevBuf kv_k, kv_v;
@@ -224,13 +257,11 @@ struct vv_ctx {
 // ------------------------------------------------------------------ helpers
 static std::vector<DevBuf*> sync_bufs(vv_ctx* c) { return {&c->hf_sync, &c->cs_sync, &c->lf_sync}; }   // sync_layout.h's layout
 static unsigned* err_word(vv_ctx* c) { return (unsigned*)c->hf_sync.p + pk::ERR * pk::LINE; }
-static const bf16* W(vv_ctx* c, const std::string& n) {
-  auto it = c->w.find(n);
-  if (it == c->w.end()) return nullptr;
-  return (const bf16*)it->second.p;
-}
 
-static int need(vv_ctx* c, const std::string& n, const std::vector<int64_t>& shape) {
+// vv_finalize's one lookup: weight `n` is bound with this shape ({}: any), and its
+// pointer goes to the table entry *slot -- nothing is resolved unchecked
+template <class T>
+static int need(vv_ctx* c, const std::string& n, const std::vector<int64_t>& shape, const T** slot) {
   auto it = c->w.find(n);
   if (it == c->w.end()) FAIL("missing weight: " + n);
   if (!shape.empty() && it->second.shape != shape) {
@@ -240,36 +271,22 @@ static int need(vv_ctx* c, const std::string& n, const std::vector<int64_t>& sha
     for (auto v : shape) s += std::to_string(v) + ",";
     FAIL(s + "]");
   }
+  *slot = (const T*)it->second.p;
   return 0;
 }
 
-// An LM projection's weight operand: the bf16 matrix, or the FP8 codes + row exponents
-struct LmW {
-  const bf16* w = nullptr;
-  const unsigned char* w8 = nullptr;
-  const signed char* w8e = nullptr;
-};
-static LmW lm_w(vv_ctx* c, const std::string& n) {
-  LmW r;
-  r.w = W(c, n);
-  if (!r.w) {
-    r.w8 = (const unsigned char*)W(c, n + "8");
-    r.w8e = (const signed char*)W(c, n + "e");
-  }
-  return r;
-}
 // vv_finalize: the projection is bound either as bf16 `n` [N][K] or as the pair `n`8 [N][K] + `n`e [N]
-static int need_lm_w(vv_ctx* c, const std::string& n, int64_t N, int64_t K) {
+static int need_lm_w(vv_ctx* c, const std::string& n, int64_t N, int64_t K, LmW* slot) {
   const bool b = c->w.count(n) > 0, q = c->w.count(n + "8") > 0, e = c->w.count(n + "e") > 0;
   if (b && (q || e)) FAIL("weight " + n + " is bound both as bf16 and as FP8 (" + n + "8 / " + n + "e)");
-  if (b) return need(c, n, {N, K});
+  if (b) return need(c, n, {N, K}, &slot->w);
   if (!q && !e) FAIL("missing weight: " + n + " (bf16), or its FP8 pair " + n + "8 (codes) + " + n + "e (exponents)");
   if (!q) FAIL("missing weight: " + n + "8 (FP8 codes; only the exponents " + n + "e are bound)");
   if (!e) FAIL("missing weight: " + n + "e (FP8 row exponents; only the codes " + n + "8 are bound)");
   if (K % 64) FAIL("FP8 weight " + n + "8: K = " + std::to_string(K) + " is not a multiple of 64");
   if (c->tp_size > 1 || c->comm) FAIL("FP8 weights (" + n + "8) are not supported on a tensor-parallel engine");
-  CHK(need(c, n + "8", {N, K}));
-  CHK(need(c, n + "e", {N}));
+  CHK(need(c, n + "8", {N, K}, &slot->w8));
+  CHK(need(c, n + "e", {N}, &slot->w8e));
   c->quantized = true;
   return 0;
 }
@@ -477,6 +494,11 @@ static int convnet_alloc(ConvNet& n, int kernel) {
     r.pad_ = 0;
     n.rolls.push_back(r);
   }
+  for (int i = 0; i < n.nst; ++i)
+    for (int j = 0; j < n.depth[i]; ++j) {
+      n.blk[i][j].mix = n.mix[i][j].base;
+      n.blk[i][j].mix_sB = n.mix[i][j].sB;
+    }
   CHK(n.d_rolls.ensure(n.rolls.size() * sizeof(RollDesc)));
   HIPCHK(hipMemcpy(n.d_rolls.p, n.rolls.data(), n.rolls.size() * sizeof(RollDesc), hipMemcpyHostToDevice));
   // transient work: X per stage + A (normed rows) + F (ffn hidden)
@@ -501,47 +523,54 @@ static int convnet_alloc(ConvNet& n, int kernel) {
   return 0;
 }
 
+// vv_finalize: the net's weights, checked and resolved (the shapes depend on the
+// channels only, so the table holds when vv_*_encode lays the net out again)
 static int convnet_check(vv_ctx* c, ConvNet& n) {
   const std::string& p = n.wp;
   const int k = 7;
   if (n.decoder) {
-    CHK(need(c, p + ".stem_w", {n.chans[0], (int64_t)k * n.in_ch}));
+    CHK(need(c, p + ".stem_w", {n.chans[0], (int64_t)k * n.in_ch}, &n.stem_w));
   } else {
-    CHK(need(c, p + ".stem_w", {n.chans[0], (int64_t)k}));
+    CHK(need(c, p + ".stem_w", {n.chans[0], (int64_t)k}, &n.stem_w));
   }
-  CHK(need(c, p + ".stem_b", {n.chans[0]}));
+  CHK(need(c, p + ".stem_b", {n.chans[0]}, &n.stem_b));
+  n.blk.assign(n.nst, {});
   for (int i = 0; i < n.nst; ++i) {
     const int C = n.chans[i];
     if (i > 0) {
       const std::string t = p + ".tr" + std::to_string(i);
       const int Ci = n.chans[i - 1], r = n.rat[i];
       if (n.decoder) {
-        CHK(need(c, t + "_w", {(int64_t)r * C, 2LL * Ci}));
-        CHK(need(c, t + "_b", {(int64_t)r * C}));
+        CHK(need(c, t + "_w", {(int64_t)r * C, 2LL * Ci}, &n.tr_w[i]));
+        CHK(need(c, t + "_b", {(int64_t)r * C}, &n.tr_b[i]));
       } else {
-        CHK(need(c, t + "_w", {C, 2LL * r * Ci}));
-        CHK(need(c, t + "_b", {C}));
+        CHK(need(c, t + "_w", {C, 2LL * r * Ci}, &n.tr_w[i]));
+        CHK(need(c, t + "_b", {C}, &n.tr_b[i]));
       }
     }
+    n.blk[i].assign(n.depth[i], Block1D{});
     for (int j = 0; j < n.depth[i]; ++j) {
       const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-      CHK(need(c, b + ".dw_w", {C, k}));
-      CHK(need(c, b + ".dw_b", {C}));
-      CHK(need(c, b + ".gamma", {C}));
-      CHK(need(c, b + ".fc1_w", {4LL * C, C}));
-      CHK(need(c, b + ".fc1_b", {4LL * C}));
-      CHK(need(c, b + ".fc2_w", {C, 4LL * C}));
-      CHK(need(c, b + ".fc2_b", {C}));
-      CHK(need(c, b + ".ffn_gamma", {C}));
+      Block1D& B = n.blk[i][j];
+      CHK(need(c, b + ".norm", {C}, &B.norm));
+      CHK(need(c, b + ".dw_w", {C, k}, &B.dw_w));
+      CHK(need(c, b + ".dw_b", {C}, &B.dw_b));
+      CHK(need(c, b + ".gamma", {C}, &B.gamma));
+      CHK(need(c, b + ".ffn_norm", {C}, &B.ffn_norm));
+      CHK(need(c, b + ".fc1_w", {4LL * C, C}, &B.fc1_w));
+      CHK(need(c, b + ".fc1_b", {4LL * C}, &B.fc1_b));
+      CHK(need(c, b + ".fc2_w", {C, 4LL * C}, &B.fc2_w));
+      CHK(need(c, b + ".fc2_b", {C}, &B.fc2_b));
+      CHK(need(c, b + ".ffn_gamma", {C}, &B.ffn_gamma));
     }
   }
   const int Cl = n.chans[n.nst - 1];
   if (n.decoder) {
-    CHK(need(c, p + ".head_w", {k, Cl}));
-    CHK(need(c, p + ".head_b", {1}));
+    CHK(need(c, p + ".head_w", {k, Cl}, &n.head_w));
+    CHK(need(c, p + ".head_b", {1}, &n.head_b));
   } else {
-    CHK(need(c, p + ".head_w", {n.out_ch, (int64_t)k * Cl}));
-    CHK(need(c, p + ".head_b", {n.out_ch}));
+    CHK(need(c, p + ".head_w", {n.out_ch, (int64_t)k * Cl}, &n.head_w));
+    CHK(need(c, p + ".head_b", {n.out_ch}, &n.head_b));
   }
   return 0;
 }
@@ -659,313 +688,272 @@ extern "C" int vv_codec_wide_active(vv_ctx* c, int n) {   // 1: some acoustic-de
 // diffusion steps whose adaLN modulations are computed in one GEMM
 static constexpr int HEAD_SC = 16;
 
+// ------------------------------------------------------------------ codec run
+// Stage i of one convnet_run call: n samples (slots[n]) of T rows x C channels
+struct StageRun {
+  ConvNet& net;
+  int i, n, T, C;
+  const int* slots;
+  float eps;
+  RowMap out;   // the last block's output rows: the next transition's input rows, or the head conv's
+  hipStream_t st;
+};
+
+// A Block1D record into the launch-per-block kernels' argument structs
+static void set_block(MixArgs& m, const Block1D& b) {
+  m.buf = b.mix;
+  m.buf_sB = b.mix_sB;
+  m.norm_w = b.norm;
+  m.dw_w = b.dw_w;
+  m.dw_b = b.dw_b;
+  m.gamma = b.gamma;
+  m.ffn_norm_w = b.ffn_norm;
+}
+static void set_block(ATransform& x, const Block1D& b) {
+  x.buf = b.mix;
+  x.buf_sB = b.mix_sB;
+  x.w = b.norm;
+  x.dw_w = b.dw_w;
+  x.dw_b = b.dw_b;
+  x.gamma = b.gamma;
+  x.ffn_w = b.ffn_norm;
+}
+static void set_block(BlockArgs& a, const Block1D& b) {   // (a.mix: mix_args)
+  a.w1 = b.fc1_w;
+  a.b1 = b.fc1_b;
+  a.w2 = b.fc2_w;
+  a.b2 = b.fc2_b;
+  a.g2 = b.ffn_gamma;
+}
+// block j's front half (k_mix, k_block) but for its x / y / a rows
+static MixArgs mix_args(const StageRun& s, int j) {
+  MixArgs mx;
+  memset(&mx, 0, sizeof(mx));
+  mx.n = s.n;
+  mx.T = s.T;
+  mx.C = s.C;
+  mx.R = std::max(1, std::min(s.T, 2048 / s.C));   // R * C / 8 = 256 conv items: one per thread
+  mx.eps = s.eps;
+  mx.ctx = s.net.mix[s.i][j].ctx;
+  mx.slots = s.slots;
+  set_block(mx, s.net.blk[s.i][j]);
+  return mx;
+}
+
+// the stem conv: stem rows -> X[0]
+static int convnet_stem(vv_ctx* c, ConvNet& net, int n, const int* slots, hipStream_t st) {
+  const int T = net.T[0], C = net.chans[0], k = 7;
+  RowMap xo = rowmap(net.X[0], C, T, (long long)T * C);
+  if (net.decoder) {
+    RowMap a = rowmap(net.stem.base, net.stem.C, T, net.stem.sB, slots);
+    return gemm(c, gemm_args(c, n * T, C, k * net.in_ch, a, net.stem_w, EPI_STORE, xo, net.stem_b), st);
+  }
+  ConvIn1Args a{n * T, C, k, rowmap(net.stem.base, 1, T, net.stem.sB, slots), net.stem_w, net.stem_b, xo};
+  KCHK(launch_conv_cin1(a, st));
+  return 0;
+}
+
+// the transition conv before stage i: tr[i] rows -> X[i]
+static int convnet_transition(vv_ctx* c, ConvNet& net, int i, int n, const int* slots, hipStream_t st) {
+  const ConvBuf& tb = net.tr[i];
+  const int T = net.T[i], C = net.chans[i], Ci = net.chans[i - 1], r = net.rat[i];
+  if (net.decoder) {
+    // 2-tap ConvTranspose: input row t = buffer rows [t, t+1] (1 history row)
+    RowMap a = rowmap(tb.base, Ci, net.Tin[i], tb.sB, slots);
+    RowMap o = rowmap(net.X[i], (long long)r * C, net.Tin[i], (long long)T * C);
+    return gemm(c, gemm_args(c, n * net.Tin[i], r * C, 2 * Ci, a, net.tr_w[i], EPI_STORE, o, net.tr_b[i]), st);
+  }
+  // strided causal conv, k = 2r, ctx = r: output row t = buffer rows [t*r, t*r + 2r)
+  RowMap a = rowmap(tb.base, (long long)r * Ci, T, tb.sB, slots);
+  RowMap X = rowmap(net.X[i], C, T, (long long)T * C);
+  return gemm(c, gemm_args(c, n * T, C, 2 * r * Ci, a, net.tr_w[i], EPI_STORE, X, net.tr_b[i]), st);
+}
+
+// the head conv (disable_last_norm: no final norm, modular_vibevoice_tokenizer.py:908-911)
+static int convnet_head(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap out, RowMap out2, hipStream_t st) {
+  const int Tl = net.T[net.nst - 1], Cl = net.chans[net.nst - 1], k = 7;
+  RowMap a = rowmap(net.head.base, Cl, Tl, net.head.sB, slots);
+  if (!net.decoder) return gemm(c, gemm_args(c, n * Tl, net.out_ch, k * Cl, a, net.head_w, EPI_STORE, out, net.head_b), st);
+  Conv1Args h{n * Tl, Cl, k, a, net.head_w, net.head_b, out, out2};
+  KCHK(launch_conv_cout1(h, st));
+  return 0;
+}
+
+// the whole narrow stage in one launch (codec_tile.hip): + the transition `pre`
+// before it and, with CT_POST_HEAD, the decoder's head conv (-> audio, audio2)
+static int stage_tile(const StageRun& s, int pre, int post, RowMap audio, RowMap audio2) {
+  ConvNet& net = s.net;
+  CodecTileArgs A;
+  memset(&A, 0, sizeof(A));
+  A.n = s.n;
+  A.T = s.T;
+  A.depth = net.depth[s.i];
+  A.eps = s.eps;
+  A.slots = s.slots;
+  A.x = net.X[s.i];
+  if (pre != CT_PRE_NONE) {
+    const bool stem = pre == CT_PRE_STEM;
+    const ConvBuf& pb = stem ? net.stem : net.tr[s.i];
+    A.pre_buf = pb.base;
+    A.pre_sB = pb.sB;
+    A.pre_w = stem ? net.stem_w : net.tr_w[s.i];
+    A.pre_b = stem ? net.stem_b : net.tr_b[s.i];
+  }
+  for (int j = 0; j < net.depth[s.i]; ++j) A.b[j] = net.blk[s.i][j];
+  if (post == CT_POST_HEAD) {
+    A.head_w = net.head_w;
+    A.head_b = net.head_b;
+    A.head_buf = net.head.base;
+    A.head_sB = net.head.sB;
+    A.audio = audio;
+    A.audio2 = audio2;
+  } else {
+    A.out = s.out;
+  }
+  const int C = s.C;
+  if (unsigned long long* sp = g_codec_tile_stamps.load())
+    A.stamps = sp + 4096 * (3 * (net.decoder ? 0 : 1) + (C == 128 ? (net.decoder ? 0 : 2) : C == 64 ? 1 : (net.decoder ? 2 : 0)));
+  KCHK(launch_codec_tile(A, C, pre, post, s.st));
+  return 0;
+}
+
+// the whole wide stage in one launch of clusters (codec_wide.hip)
+static int stage_wide(vv_ctx* c, const StageRun& s) {
+  ConvNet& net = s.net;
+  const int C = s.C;
+  CodecWideArgs A;
+  memset(&A, 0, sizeof(A));
+  A.n = s.n;
+  A.T = s.T;
+  A.depth = net.depth[s.i];
+  A.eps = s.eps;
+  A.slots = s.slots;
+  A.x = net.X[s.i];
+  for (int j = 0; j < net.depth[s.i]; ++j) A.b[j] = net.blk[s.i][j];
+  A.out = s.out;
+  CHK(c->cw_slab.ensure(codec_wide_slab_floats(C, s.T, s.n) * sizeof(float)));
+  CHK(c->cw_xbuf.ensure(codec_wide_xbuf_elems(C, s.T, s.n) * sizeof(bf16)));
+  A.sync = (unsigned*)c->cw_sync.p + (C == 512 ? pk::CW_HALF : 0);
+  A.err = err_word(c);
+  A.slab = (float*)c->cw_slab.p;
+  A.xbuf = (bf16*)c->cw_xbuf.p;
+  if (unsigned long long* sp = g_codec_wide_stamps.load()) A.stamps = sp + 8192 * (2 * (net.decoder ? 0 : 1) + (C == 512));
+  const int rc = launch_codec_wide(A, C, s.st);
+  if (rc) FAIL("wide codec stage: launch failed (" + std::to_string(rc) + ")");
+  return 0;
+}
+
+// the whole stage (one sample) in one persistent launch (codec_stage.hip)
+static int stage_persistent(vv_ctx* c, const StageRun& s) {
+  ConvNet& net = s.net;
+  CodecStageArgs A;
+  memset(&A, 0, sizeof(A));
+  A.depth = net.depth[s.i];
+  A.ctx = net.mix[s.i][0].ctx;
+  A.C = s.C;
+  A.M = s.T;
+  A.eps = s.eps;
+  A.slots = s.slots;
+  A.x = net.X[s.i];
+  A.xe = net.Y[s.i];
+  A.h = net.F;
+  A.out = s.out;
+  for (int j = 0; j < net.depth[s.i]; ++j) {
+    A.b[j] = net.blk[s.i][j];
+    if (net.mix[s.i][j].ctx != A.ctx) FAIL("codec stage: conv buffers of one stage differ in history length");
+  }
+  A.sync = (unsigned*)c->cs_sync.p;
+  A.err = err_word(c);
+  A.stamps = net.decoder && s.i == g_codec_stage_stamp_at ? g_codec_stage_stamps.load() : nullptr;
+  const int v = (g_codec_stage.load() >> 1) & 7;
+  A.pubfirst = v ? v - 1 : 5;
+  const int rc = launch_codec_stage(A, s.st);
+  if (rc) FAIL("persistent codec stage: launch failed (" + std::to_string(rc) + ": " +
+               hipGetErrorString(hipGetLastError()) + ")");
+  return 0;
+}
+
+// narrow stage: each Block1D is one k_block launch; the residual ping-pongs
+// X -> Y -> X (a workgroup reads halo rows other workgroups own)
+static int stage_blocks(const StageRun& s) {
+  ConvNet& net = s.net;
+  const int i = s.i;
+  for (int j = 0; j < net.depth[i]; ++j) {
+    BlockArgs ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.mix = mix_args(s, j);
+    ba.mix.x = (j & 1) ? net.Y[i] : net.X[i];
+    set_block(ba, net.blk[i][j]);
+    ba.out = j == net.depth[i] - 1 ? s.out : rowmap((j & 1) ? net.X[i] : net.Y[i], s.C, s.T, (long long)s.T * s.C);
+    KCHK(launch_block(ba, s.st));
+  }
+  return 0;
+}
+
+// per Block1D: the front half (k_mix, or fc1's prologue), fc1 and fc2 GEMMs
+static int stage_gemms(vv_ctx* c, const StageRun& s) {
+  ConvNet& net = s.net;
+  const int i = s.i, n = s.n, T = s.T, C = s.C;
+  RowMap X = rowmap(net.X[i], C, T, (long long)T * C);
+  RowMap Y = rowmap(net.Y[i], C, T, (long long)T * C);
+  RowMap Fm = rowmap(net.F, 4LL * C);
+  for (int j = 0; j < net.depth[i]; ++j) {
+    const Block1D& B = net.blk[i][j];
+    if ((g_mix_fusion & 1) && gemv_mix_lds(n * T, T, C)) {
+      // few rows (T = 1, 8 stages at small batch): the mix runs in fc1's prologue
+      GemmArgs g = gemm_args(c, n * T, 4 * C, C, X, B.fc1_w, EPI_GELU, Fm, B.fc1_b);
+      g.xf.kind = XF_MIX;
+      g.xf.eps = s.eps;
+      g.xf.T = T;
+      g.xf.ctx = net.mix[i][j].ctx;
+      g.xf.slots = s.slots;
+      set_block(g.xf, B);
+      g.xf.y = net.Y[i];
+      CHK(gemm(c, g, s.st));
+    } else {
+      // mixer norm + depthwise conv + gamma residual (X -> Y) + ffn_norm (-> A), one launch
+      MixArgs mx = mix_args(s, j);
+      mx.x = net.X[i];
+      mx.y = net.Y[i];
+      mx.a = net.A;
+      KCHK(launch_mix(mx, s.st));
+      CHK(gemm(c, gemm_args(c, n * T, 4 * C, C, rowmap(net.A, C), B.fc1_w, EPI_GELU, Fm, B.fc1_b), s.st));
+    }
+    GemmArgs g = gemm_args(c, n * T, C, 4 * C, Fm, B.fc2_w, EPI_RES, j == net.depth[i] - 1 ? s.out : X, B.fc2_b);
+    g.epi.res = Y;
+    g.epi.gamma = B.ffn_gamma;
+    CHK(gemm(c, g, s.st));
+  }
+  return 0;
+}
+
 // One block stack + transitions.  n active samples (slots[n]); input rows already
 // in `stem` (rows [ctx, ctx+T0)).  Decoder: writes audio to out (+ out2).
 // Encoder: writes [n, out_ch] features to out.
 static int convnet_run(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap out, RowMap out2, hipStream_t st) {
-  const std::string& p = net.wp;
-  const float eps = c->cfg.codec_eps;
-  const int k = 7;
-  // ---- stem (the encoders' is fused into stage 0's tile launch where it applies)
-  if (net.decoder || tile_pre(net, 0) != CT_PRE_STEM) {
-    const int T = net.T[0], C = net.chans[0];
-    RowMap xo = rowmap(net.X[0], C, T, (long long)T * C);
-    if (net.decoder) {
-      RowMap a = rowmap(net.stem.base, net.stem.C, T, net.stem.sB, slots);
-      GemmArgs g = gemm_args(c, n * T, C, k * net.in_ch, a, W(c, p + ".stem_w"), EPI_STORE, xo, W(c, p + ".stem_b"));
-      CHK(gemm(c, g, st));
-    } else {
-      ConvIn1Args a;
-      a.M = n * T;
-      a.C = C;
-      a.K = k;
-      a.buf = rowmap(net.stem.base, 1, T, net.stem.sB, slots);
-      a.w = W(c, p + ".stem_w");
-      a.b = W(c, p + ".stem_b");
-      a.out = xo;
-      KCHK(launch_conv_cin1(a, st));
-    }
-  }
+  // (the encoders' stem is fused into stage 0's tile launch where it applies)
+  if (net.decoder || tile_pre(net, 0) != CT_PRE_STEM) CHK(convnet_stem(c, net, n, slots, st));
   bool head_done = false;
   for (int i = 0; i < net.nst; ++i) {
     const int T = net.T[i], C = net.chans[i];
-    RowMap X = rowmap(net.X[i], C, T, (long long)T * C);
     const int tpre = tile_pre(net, i);
-    if (i > 0 && tpre != CT_PRE_CONVT && tpre != CT_PRE_SCONV) {
-      const ConvBuf& tb = net.tr[i];
-      const int Ci = net.chans[i - 1], r = net.rat[i];
-      const std::string t = p + ".tr" + std::to_string(i);
-      if (net.decoder) {
-        // 2-tap ConvTranspose: input row t = buffer rows [t, t+1] (1 history row)
-        RowMap a = rowmap(tb.base, Ci, net.Tin[i], tb.sB, slots);
-        RowMap o = rowmap(net.X[i], (long long)r * C, net.Tin[i], (long long)T * C);
-        GemmArgs g = gemm_args(c, n * net.Tin[i], r * C, 2 * Ci, a, W(c, t + "_w"), EPI_STORE, o, W(c, t + "_b"));
-        CHK(gemm(c, g, st));
-      } else {
-        // strided causal conv, k = 2r, ctx = r: output row t = buffer rows [t*r, t*r + 2r)
-        RowMap a = rowmap(tb.base, (long long)r * Ci, T, tb.sB, slots);
-        GemmArgs g = gemm_args(c, n * T, C, 2 * r * Ci, a, W(c, t + "_w"), EPI_STORE, X, W(c, t + "_b"));
-        CHK(gemm(c, g, st));
-      }
-    }
+    if (i > 0 && tpre != CT_PRE_CONVT && tpre != CT_PRE_SCONV) CHK(convnet_transition(c, net, i, n, slots, st));
+    const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
+    const StageRun s{net, i, n, T, C, slots, c->cfg.codec_eps, buf_in_rows(nb, T, slots), st};
     if (tpre >= 0) {
-      // the whole narrow stage in one launch (codec_tile.hip)
-      CodecTileArgs A;
-      memset(&A, 0, sizeof(A));
-      A.n = n;
-      A.T = T;
-      A.depth = net.depth[i];
-      A.eps = eps;
-      A.slots = slots;
-      A.x = net.X[i];
-      if (tpre == CT_PRE_STEM) {
-        A.pre_buf = net.stem.base;
-        A.pre_sB = net.stem.sB;
-        A.pre_w = W(c, p + ".stem_w");
-        A.pre_b = W(c, p + ".stem_b");
-      } else if (tpre != CT_PRE_NONE) {
-        const std::string t = p + ".tr" + std::to_string(i);
-        A.pre_buf = net.tr[i].base;
-        A.pre_sB = net.tr[i].sB;
-        A.pre_w = W(c, t + "_w");
-        A.pre_b = W(c, t + "_b");
-      }
-      for (int j = 0; j < net.depth[i]; ++j) {
-        const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-        CodecTileBlock& Bk = A.b[j];
-        Bk.norm = W(c, b + ".norm");
-        Bk.dw_w = W(c, b + ".dw_w");
-        Bk.dw_b = W(c, b + ".dw_b");
-        Bk.gamma = W(c, b + ".gamma");
-        Bk.ffn_norm = W(c, b + ".ffn_norm");
-        Bk.fc1_w = W(c, b + ".fc1_w");
-        Bk.fc1_b = W(c, b + ".fc1_b");
-        Bk.fc2_w = W(c, b + ".fc2_w");
-        Bk.fc2_b = W(c, b + ".fc2_b");
-        Bk.ffn_gamma = W(c, b + ".ffn_gamma");
-        Bk.mix = net.mix[i][j].base;
-        Bk.mix_sB = net.mix[i][j].sB;
-      }
-      int post = CT_POST_NONE;
-      if (net.decoder && i == net.nst - 1) {
-        post = CT_POST_HEAD;
-        A.head_w = W(c, p + ".head_w");
-        A.head_b = W(c, p + ".head_b");
-        A.head_buf = net.head.base;
-        A.head_sB = net.head.sB;
-        A.audio = out;
-        A.audio2 = out2;
-        head_done = true;
-      } else {
-        const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-        A.out = buf_in_rows(nb, T, slots);
-      }
-      if (unsigned long long* sp = g_codec_tile_stamps.load())
-        A.stamps = sp + 4096 * (3 * (net.decoder ? 0 : 1) + (C == 128 ? (net.decoder ? 0 : 2) : C == 64 ? 1 : (net.decoder ? 2 : 0)));
-      KCHK(launch_codec_tile(A, C, tpre, post, st));
-      continue;
-    }
-    if (wide_on(c, net, i, n)) {
-      // the whole wide stage in one launch of clusters (codec_wide.hip)
-      CodecWideArgs A;
-      memset(&A, 0, sizeof(A));
-      A.n = n;
-      A.T = T;
-      A.depth = net.depth[i];
-      A.eps = eps;
-      A.slots = slots;
-      A.x = net.X[i];
-      for (int j = 0; j < net.depth[i]; ++j) {
-        const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-        CodecTileBlock& Bk = A.b[j];
-        Bk.norm = W(c, b + ".norm");
-        Bk.dw_w = W(c, b + ".dw_w");
-        Bk.dw_b = W(c, b + ".dw_b");
-        Bk.gamma = W(c, b + ".gamma");
-        Bk.ffn_norm = W(c, b + ".ffn_norm");
-        Bk.fc1_w = W(c, b + ".fc1_w");
-        Bk.fc1_b = W(c, b + ".fc1_b");
-        Bk.fc2_w = W(c, b + ".fc2_w");
-        Bk.fc2_b = W(c, b + ".fc2_b");
-        Bk.ffn_gamma = W(c, b + ".ffn_gamma");
-        Bk.mix = net.mix[i][j].base;
-        Bk.mix_sB = net.mix[i][j].sB;
-      }
-      const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-      A.out = buf_in_rows(nb, T, slots);
-      CHK(c->cw_slab.ensure(codec_wide_slab_floats(C, T, n) * sizeof(float)));
-      CHK(c->cw_xbuf.ensure(codec_wide_xbuf_elems(C, T, n) * sizeof(bf16)));
-      A.sync = (unsigned*)c->cw_sync.p + (C == 512 ? pk::CW_HALF : 0);
-      A.err = err_word(c);
-      A.slab = (float*)c->cw_slab.p;
-      A.xbuf = (bf16*)c->cw_xbuf.p;
-      if (unsigned long long* sp = g_codec_wide_stamps.load()) A.stamps = sp + 8192 * (2 * (net.decoder ? 0 : 1) + (C == 512));
-      const int rc = launch_codec_wide(A, C, st);
-      if (rc) FAIL("wide codec stage: launch failed (" + std::to_string(rc) + ")");
-      continue;
-    }
-    if (codec_stage_on(c, net, i, n)) {
-      // the whole stage (one sample) in one persistent launch (codec_stage.hip)
-      CodecStageArgs A;
-      memset(&A, 0, sizeof(A));
-      A.depth = net.depth[i];
-      A.ctx = net.mix[i][0].ctx;
-      A.C = C;
-      A.M = T;
-      A.eps = eps;
-      A.slots = slots;
-      A.x = net.X[i];
-      A.xe = net.Y[i];
-      A.h = net.F;
-      const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-      A.out = buf_in_rows(nb, T, slots);
-      for (int j = 0; j < net.depth[i]; ++j) {
-        const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-        CodecStageBlock& B = A.b[j];
-        B.norm = W(c, b + ".norm");
-        B.dw_w = W(c, b + ".dw_w");
-        B.dw_b = W(c, b + ".dw_b");
-        B.gamma = W(c, b + ".gamma");
-        B.ffn_norm = W(c, b + ".ffn_norm");
-        B.fc1_w = W(c, b + ".fc1_w");
-        B.fc1_b = W(c, b + ".fc1_b");
-        B.fc2_w = W(c, b + ".fc2_w");
-        B.fc2_b = W(c, b + ".fc2_b");
-        B.ffn_gamma = W(c, b + ".ffn_gamma");
-        B.mix = net.mix[i][j].base;
-        B.mix_sB = net.mix[i][j].sB;
-        if (net.mix[i][j].ctx != A.ctx) FAIL("codec stage: conv buffers of one stage differ in history length");
-      }
-      A.sync = (unsigned*)c->cs_sync.p;
-      A.err = err_word(c);
-      A.stamps = net.decoder && i == g_codec_stage_stamp_at ? g_codec_stage_stamps.load() : nullptr;
-      {
-        const int v = (g_codec_stage.load() >> 1) & 7;
-        A.pubfirst = v ? v - 1 : 5;
-      }
-      const int rc = launch_codec_stage(A, st);
-      if (rc) FAIL("persistent codec stage: launch failed (" + std::to_string(rc) + ": " +
-                   hipGetErrorString(hipGetLastError()) + ")");
-      continue;
-    }
-    const int Rb = std::max(1, std::min(T, 2048 / C));
-    if ((g_mix_fusion & 2) && block_lds(Rb, C)) {
-      // narrow stage: each Block1D is one k_block launch; the residual
-      // ping-pongs X -> Y -> X (a workgroup reads halo rows other workgroups own)
-      for (int j = 0; j < net.depth[i]; ++j) {
-        const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-        const ConvBuf& mb = net.mix[i][j];
-        BlockArgs ba;
-        memset(&ba, 0, sizeof(ba));
-        MixArgs& mx = ba.mix;
-        mx.n = n;
-        mx.T = T;
-        mx.C = C;
-        mx.R = Rb;
-        mx.eps = eps;
-        mx.ctx = mb.ctx;
-        mx.x = (j & 1) ? net.Y[i] : net.X[i];
-        mx.buf = mb.base;
-        mx.buf_sB = mb.sB;
-        mx.slots = slots;
-        mx.norm_w = W(c, b + ".norm");
-        mx.dw_w = W(c, b + ".dw_w");
-        mx.dw_b = W(c, b + ".dw_b");
-        mx.gamma = W(c, b + ".gamma");
-        mx.ffn_norm_w = W(c, b + ".ffn_norm");
-        ba.w1 = W(c, b + ".fc1_w");
-        ba.b1 = W(c, b + ".fc1_b");
-        ba.w2 = W(c, b + ".fc2_w");
-        ba.b2 = W(c, b + ".fc2_b");
-        ba.g2 = W(c, b + ".ffn_gamma");
-        if (j == net.depth[i] - 1) {
-          const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-          ba.out = buf_in_rows(nb, T, slots);
-        } else {
-          ba.out = rowmap((j & 1) ? net.X[i] : net.Y[i], C, T, (long long)T * C);
-        }
-        KCHK(launch_block(ba, st));
-      }
-      continue;
-    }
-    for (int j = 0; j < net.depth[i]; ++j) {
-      const std::string b = p + ".s" + std::to_string(i) + ".b" + std::to_string(j);
-      const ConvBuf& mb = net.mix[i][j];
-      RowMap Y = rowmap(net.Y[i], C, T, (long long)T * C);
-      RowMap Fm = rowmap(net.F, 4LL * C);
-      if ((g_mix_fusion & 1) && gemv_mix_lds(n * T, T, C)) {
-        // few rows (T = 1, 8 stages at small batch): the mix runs in fc1's prologue
-        GemmArgs g = gemm_args(c, n * T, 4 * C, C, X, W(c, b + ".fc1_w"), EPI_GELU, Fm, W(c, b + ".fc1_b"));
-        g.xf.kind = XF_MIX;
-        g.xf.eps = eps;
-        g.xf.w = W(c, b + ".norm");
-        g.xf.T = T;
-        g.xf.ctx = mb.ctx;
-        g.xf.buf = mb.base;
-        g.xf.buf_sB = mb.sB;
-        g.xf.slots = slots;
-        g.xf.dw_w = W(c, b + ".dw_w");
-        g.xf.dw_b = W(c, b + ".dw_b");
-        g.xf.gamma = W(c, b + ".gamma");
-        g.xf.ffn_w = W(c, b + ".ffn_norm");
-        g.xf.y = net.Y[i];
-        CHK(gemm(c, g, st));
-      } else {
-      // mixer norm + depthwise conv + gamma residual (X -> Y) + ffn_norm (-> A), one launch
-      MixArgs mx;
-      memset(&mx, 0, sizeof(mx));
-      mx.n = n;
-      mx.T = T;
-      mx.C = C;
-      mx.R = std::max(1, std::min(T, 2048 / C));   // R * C / 8 = 256 conv items: one per thread
-      mx.eps = eps;
-      mx.ctx = mb.ctx;
-      mx.x = net.X[i];
-      mx.y = net.Y[i];
-      mx.a = net.A;
-      mx.buf = mb.base;
-      mx.buf_sB = mb.sB;
-      mx.slots = slots;
-      mx.norm_w = W(c, b + ".norm");
-      mx.dw_w = W(c, b + ".dw_w");
-      mx.dw_b = W(c, b + ".dw_b");
-      mx.gamma = W(c, b + ".gamma");
-      mx.ffn_norm_w = W(c, b + ".ffn_norm");
-      KCHK(launch_mix(mx, st));
-      CHK(gemm(c, gemm_args(c, n * T, 4 * C, C, rowmap(net.A, C), W(c, b + ".fc1_w"), EPI_GELU, Fm,
-                            W(c, b + ".fc1_b")), st));
-      }
-      RowMap o = X;
-      const bool last = j == net.depth[i] - 1;
-      if (last) {
-        const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-        o = buf_in_rows(nb, T, slots);
-      }
-      GemmArgs g = gemm_args(c, n * T, C, 4 * C, Fm, W(c, b + ".fc2_w"), EPI_RES, o, W(c, b + ".fc2_b"));
-      g.epi.res = Y;
-      g.epi.gamma = W(c, b + ".ffn_gamma");
-      CHK(gemm(c, g, st));
+      head_done = net.decoder && i == net.nst - 1;
+      CHK(stage_tile(s, tpre, head_done ? CT_POST_HEAD : CT_POST_NONE, out, out2));
+    } else if (wide_on(c, net, i, n)) {
+      CHK(stage_wide(c, s));
+    } else if (codec_stage_on(c, net, i, n)) {
+      CHK(stage_persistent(c, s));
+    } else if ((g_mix_fusion & 2) && block_lds(std::max(1, std::min(T, 2048 / C)), C)) {
+      CHK(stage_blocks(s));
+    } else {
+      CHK(stage_gemms(c, s));
     }
   }
-  // ---- head (disable_last_norm: no final norm, modular_vibevoice_tokenizer.py:908-911)
-  const int Tl = net.T[net.nst - 1], Cl = net.chans[net.nst - 1];
-  if (head_done) {
-  } else if (net.decoder) {
-    Conv1Args a;
-    a.M = n * Tl;
-    a.C = Cl;
-    a.K = k;
-    a.buf = rowmap(net.head.base, Cl, Tl, net.head.sB, slots);
-    a.w = W(c, p + ".head_w");
-    a.b = W(c, p + ".head_b");
-    a.out = out;
-    a.out2 = out2;
-    KCHK(launch_conv_cout1(a, st));
-  } else {
-    RowMap a = rowmap(net.head.base, Cl, Tl, net.head.sB, slots);
-    GemmArgs g = gemm_args(c, n * Tl, net.out_ch, k * Cl, a, W(c, p + ".head_w"), EPI_STORE, out, W(c, p + ".head_b"));
-    CHK(gemm(c, g, st));
-  }
+  if (!head_done) CHK(convnet_head(c, net, n, slots, out, out2, st));
   return 0;
 }
 
@@ -1018,6 +1006,8 @@ void vv_destroy(vv_ctx* c) {
 
 int vv_bind_weight(vv_ctx* c, const char* name, const void* p, const int64_t* shape, int ndim) {
   if (!c || !name || !p) FAIL("vv_bind_weight: null argument");
+  if (c->finalized)
+    FAIL(std::string("vv_bind_weight(") + name + ") after vv_finalize: the weight table is resolved (and captured graphs hold its pointers)");
   Weight w;
   w.p = p;
   w.shape.assign(shape, shape + ndim);
@@ -1057,19 +1047,21 @@ int vv_finalize(vv_ctx* c) {
   const int H = k.hidden, d = k.head_dim;
   c->qkv_n = (k.n_heads + 2 * k.n_kv_heads) * d;
   // ---- LM weights
-  CHK(need(c, "lm.embed", {}));
-  CHK(need(c, "lm.lm_head", {}));
-  CHK(need(c, "lm.inv_freq", {d / 2}));
-  CHK(need(c, "lm.norm", {H}));
+  CHK(need(c, "lm.embed", {}, &c->lm.embed));
+  CHK(need(c, "lm.lm_head", {}, &c->lm.lm_head));
+  CHK(need(c, "lm.inv_freq", {d / 2}, &c->lm.inv_freq));
+  CHK(need(c, "lm.norm", {H}, &c->lm.norm));
+  c->lmw.assign(k.n_layers, LmLayerW{});
   for (int l = 0; l < k.n_layers; ++l) {
     const std::string p = "lm." + std::to_string(l);
-    CHK(need(c, p + ".in_norm", {H}));
-    CHK(need_lm_w(c, p + ".qkv_w", c->qkv_n, H));
-    CHK(need(c, p + ".qkv_b", {c->qkv_n}));
-    CHK(need_lm_w(c, p + ".o_w", H, (int64_t)k.n_heads * d));
-    CHK(need(c, p + ".post_norm", {H}));
-    CHK(need_lm_w(c, p + ".gu_w", 2LL * k.intermediate, H));
-    CHK(need_lm_w(c, p + ".down_w", H, k.intermediate));
+    LmLayerW& w = c->lmw[l];
+    CHK(need(c, p + ".in_norm", {H}, &w.in_norm));
+    CHK(need_lm_w(c, p + ".qkv_w", c->qkv_n, H, &w.qkv));
+    CHK(need(c, p + ".qkv_b", {c->qkv_n}, &w.qkv_b));
+    CHK(need_lm_w(c, p + ".o_w", H, (int64_t)k.n_heads * d, &w.o));
+    CHK(need(c, p + ".post_norm", {H}, &w.post_norm));
+    CHK(need_lm_w(c, p + ".gu_w", 2LL * k.intermediate, H, &w.gu));
+    CHK(need_lm_w(c, p + ".down_w", H, k.intermediate, &w.down));
   }
   if (c->quantized) {
     // the fallback's scratch (launch_gemm: more than 16 rows, forms k_gemv_w8 does not
@@ -1079,37 +1071,38 @@ int vv_finalize(vv_ctx* c) {
   }
   // ---- diffusion head
   const int L = k.head_layers, F = k.head_ffn, D = k.latent_dim;
-  CHK(need(c, "head.noisy_w", {H, D}));
-  CHK(need(c, "head.cond_w", {H, H}));
-  CHK(need(c, "head.t0_w", {H, 256}));
-  CHK(need(c, "head.t2_w", {H, H}));
-  CHK(need(c, "head.ada_w", {(3LL * L + 2) * H, H}));
+  CHK(need(c, "head.noisy_w", {H, D}, &c->head.noisy));
+  CHK(need(c, "head.cond_w", {H, H}, &c->head.cond));
+  CHK(need(c, "head.t0_w", {H, 256}, &c->head.t0));
+  CHK(need(c, "head.t2_w", {H, H}, &c->head.t2));
+  CHK(need(c, "head.ada_w", {(3LL * L + 2) * H, H}, &c->head.ada));
   // the FFN in the GEMV layout (weights.py: 16-row gate|up tiles of 8 gate + 8 up rows)
   c->head_gemv = true;
+  c->headw.assign(L, HeadLayerW{});
   for (int l = 0; l < L; ++l) {
     const std::string p = "head." + std::to_string(l);
-    CHK(need(c, p + ".norm", {H}));
-    CHK(need(c, p + ".gu_w", {2LL * F, H}));
-    CHK(need(c, p + ".down_w", {H, F}));
+    CHK(need(c, p + ".norm", {H}, &c->headw[l].norm));
+    CHK(need(c, p + ".gu_w", {2LL * F, H}, &c->headw[l].gu));
+    CHK(need(c, p + ".down_w", {H, F}, &c->headw[l].down));
   }
-  CHK(need(c, "head.final_w", {D, H}));
+  CHK(need(c, "head.final_w", {D, H}, &c->head.final));
   // grid-wait counters + the error word (always present: vv_sync_error_async reads it)
   for (DevBuf* b : sync_bufs(c)) {
     CHK(b->ensure(pk::BYTES));
     HIPCHK(hipMemset(b->p, 0, pk::BYTES));
   }
   // ---- connectors + latent scaling
-  CHK(need(c, "conn.ac.fc1_w", {H, D}));
-  CHK(need(c, "conn.se.fc1_w", {H, k.semantic_dim}));
-  for (const char* q : {"conn.ac", "conn.se"}) {
-    const std::string s(q);
-    CHK(need(c, s + ".fc1_b", {H}));
-    CHK(need(c, s + ".norm", {H}));
-    CHK(need(c, s + ".fc2_w", {H, H}));
-    CHK(need(c, s + ".fc2_b", {H}));
+  for (int q = 0; q < 2; ++q) {
+    const std::string s(q == 0 ? "conn.ac" : "conn.se");
+    ConnW& w = q == 0 ? c->conn_ac : c->conn_se;
+    CHK(need(c, s + ".fc1_w", {H, q == 0 ? D : k.semantic_dim}, &w.fc1_w));
+    CHK(need(c, s + ".fc1_b", {H}, &w.fc1_b));
+    CHK(need(c, s + ".norm", {H}, &w.norm));
+    CHK(need(c, s + ".fc2_w", {H, H}, &w.fc2_w));
+    CHK(need(c, s + ".fc2_b", {H}, &w.fc2_b));
   }
-  CHK(need(c, "speech_scaling_factor", {}));
-  CHK(need(c, "speech_bias_factor", {}));
+  CHK(need(c, "speech_scaling_factor", {}, &c->scaling));
+  CHK(need(c, "speech_bias_factor", {}, &c->bias));
   // ---- codec nets
   const int hop = [&] {
     int h = 1;
@@ -1120,9 +1113,12 @@ int vv_finalize(vv_ctx* c) {
   convnet_shape(c, c->sem, false, "sem", k.sem_n_filters, 1, k.semantic_dim, hop, k.max_batch);
   CHK(convnet_check(c, c->dec));
   CHK(convnet_check(c, c->sem));
-  const bool has_aenc = c->w.count("aenc.stem_w") > 0;
-  if (has_aenc) {
-    convnet_shape(c, c->aenc, false, "aenc", k.ac_enc_n_filters, 1, D, hop, 1);
+  // the non-streaming encoders: weights now, buffers per call (encode_nonstreaming)
+  convnet_shape(c, c->senc, false, "sem", k.sem_n_filters, 1, k.semantic_dim, 0, 0);
+  CHK(convnet_check(c, c->senc));
+  c->has_aenc = c->w.count("aenc.stem_w") > 0;   // optional: vv_acoustic_encode fails without it
+  if (c->has_aenc) {
+    convnet_shape(c, c->aenc, false, "aenc", k.ac_enc_n_filters, 1, D, 0, 0);
     CHK(convnet_check(c, c->aenc));
   }
   CHK(convnet_alloc(c->dec, 7));
@@ -1185,7 +1181,7 @@ int vv_finalize(vv_ctx* c) {
   // RoPE cos / sin per position (the q|k|v epilogue reads it instead of cosf / sinf)
   if (d == 128) {
     CHK(c->rope_tab.ensure((size_t)c->kv.max_ctx * 128 * sizeof(bf16)));
-    KCHK(launch_rope_table(c->kv.max_ctx, (const float*)W(c, "lm.inv_freq"), (bf16*)c->rope_tab.p, nullptr));
+    KCHK(launch_rope_table(c->kv.max_ctx, c->lm.inv_freq, (bf16*)c->rope_tab.p, nullptr));
     HIPCHK(hipDeviceSynchronize());
   }
   c->kv.k = (bf16*)c->kv_k.p;
@@ -1243,9 +1239,9 @@ int vv_set_schedule(vv_ctx* c, int steps, const float* coef, const void* tfreq, 
   CHK(c->tfreq_tmp.ensure((size_t)1000 * H * sizeof(bf16)));
   // t_emb = Linear2(SiLU(Linear0(t_freq)))  (TimestepEmbedder.forward, diffusion_head.py:90-93)
   bf16* t1 = (bf16*)c->tfreq_tmp.p;
-  CHK(gemm(c, gemm_args(c, steps, H, 256, rowmap(tfreq, 256), W(c, "head.t0_w"), EPI_STORE, rowmap(t1, H)), st));
+  CHK(gemm(c, gemm_args(c, steps, H, 256, rowmap(tfreq, 256), c->head.t0, EPI_STORE, rowmap(t1, H)), st));
   KCHK(launch_silu(steps * H, t1, t1, st));
-  CHK(gemm(c, gemm_args(c, steps, H, H, rowmap(t1, H), W(c, "head.t2_w"), EPI_STORE, rowmap(c->temb.p, H)), st));
+  CHK(gemm(c, gemm_args(c, steps, H, H, rowmap(t1, H), c->head.t2, EPI_STORE, rowmap(c->temb.p, H)), st));
   c->steps = steps;
   HIPCHK(hipStreamSynchronize(st));
   return 0;
@@ -1270,8 +1266,9 @@ int vv_kv_synthetic(vv_ctx* c, int n, const int* slots, int p0, int p1, unsigned
 }
 
 int vv_embed(vv_ctx* c, int n, const int* ids, void* out, vv_stream vst) {
+  if (!c->finalized) FAIL("vv_embed before vv_finalize");
   const int H = c->cfg.hidden;
-  KCHK(launch_gather_rows(n, H, W(c, "lm.embed"), H, ids, rowmap(out, H), (hipStream_t)vst));
+  KCHK(launch_gather_rows(n, H, c->lm.embed, H, ids, rowmap(out, H), (hipStream_t)vst));
   return 0;
 }
 
@@ -1327,7 +1324,6 @@ struct LmPass {
   bf16 *h = nullptr, *q = nullptr, *att = nullptr, *act = nullptr;
   RowMap in_m, hm;
   const int *slot = nullptr, *pos = nullptr;
-  const float* inv_freq = nullptr;
 };
 
 // The decode attention's plan for a pass of ntok rows over max_pos_p1 keys
@@ -1420,7 +1416,6 @@ static int lm_begin(vv_ctx* c, LmPass& P, int ntok, const void* embeds, int embe
   P.hm = rowmap(P.h, H);
   P.slot = slot;
   P.pos = pos;
-  P.inv_freq = (const float*)W(c, "lm.inv_freq");
   return 0;
 }
 
@@ -1470,19 +1465,19 @@ extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
 static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, d = k.head_dim, nhd = k.n_heads * d;
-  const std::string p = "lm." + std::to_string(l);
+  const LmLayerW& w = c->lmw[l];
   {
     // input_layernorm -> q|k|v projection (+bias) -> RoPE -> q / KV cache, one launch
-    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, lm_w(c, p + ".qkv_w"), EPI_ROPE, RowMap{},
-                           W(c, p + ".qkv_b"));
-    g.xf = xf_norm(W(c, p + ".in_norm"), k.rms_eps);
+    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, w.qkv, EPI_ROPE, RowMap{},
+                           w.qkv_b);
+    g.xf = xf_norm(w.in_norm, k.rms_eps);
     g.rope.nh = k.n_heads;
     g.rope.nkv = k.n_kv_heads;
     g.rope.layer = l;
     g.rope.q_out = P.q;
     g.rope.slots = P.slot;
     g.rope.pos = P.pos;
-    g.rope.inv_freq = P.inv_freq;
+    g.rope.inv_freq = c->lm.inv_freq;
     g.rope.cs_tab = g_rope_tab ? (const bf16*)c->rope_tab.p : nullptr;
     g.rope.kv = c->kv;
     if (c->kv_dtype) {
@@ -1500,11 +1495,11 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       LmAttnArgs a;
       memset(&a, 0, sizeof(a));
       a.qkv = g;
-      a.nw = W(c, p + ".in_norm");
+      a.nw = w.in_norm;
       a.eps = k.rms_eps;
       a.scale = 1.0f / sqrtf((float)d);
       a.R = P.ntok;
-      a.ow = W(c, p + ".o_w");
+      a.ow = w.o.w;
       a.res = l == 0 ? P.in_m : P.hm;
       a.out = P.hm;
       a.att = P.att;
@@ -1548,7 +1543,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     at.part_ml2 = at.part_o2 + (size_t)P.ntok * k.n_heads * P.ngroups * d;
   }
   KCHK(launch_attn(at, st));
-  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), lm_w(c, p + ".o_w"), EPI_RES, P.hm);
+  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), w.o, EPI_RES, P.hm);
   if (P.defer) {
     g.xf.kind = XF_ATTN_MERGE;
     g.xf.part_o = at.part_o;
@@ -1599,7 +1594,7 @@ extern "C" int vv_lm_ffn_active(vv_ctx* c, int ntok) {
 static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, I = k.intermediate;
-  const std::string p = "lm." + std::to_string(l);
+  const LmLayerW& w = c->lmw[l];
   if (lm_ffn_on(c, P)) {
     LmFfnArgs a;
     memset(&a, 0, sizeof(a));
@@ -1608,9 +1603,9 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     a.ldx = H;
     a.R = P.ntok;
     a.eps = k.rms_eps;
-    a.nw = W(c, p + ".post_norm");
-    a.gu = W(c, p + ".gu_w");
-    a.dn = W(c, p + ".down_w");
+    a.nw = w.post_norm;
+    a.gu = w.gu.w;
+    a.dn = w.down.w;
     a.act = P.act;
     a.sync = (unsigned*)c->lf_sync.p;
     a.err = err_word(c);
@@ -1621,9 +1616,9 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     return 0;
   }
   // post_attention_layernorm fused into gate|up's A load
-  GemmArgs g = gemm_args(c, P.ntok, 2 * I, H, P.hm, lm_w(c, p + ".gu_w"), EPI_SILU_MUL, rowmap(P.act, I));
-  g.xf = xf_norm(W(c, p + ".post_norm"), k.rms_eps);
-  GemmArgs d = gemm_args(c, P.ntok, H, I, rowmap(P.act, I), lm_w(c, p + ".down_w"), EPI_RES, P.hm);
+  GemmArgs g = gemm_args(c, P.ntok, 2 * I, H, P.hm, w.gu, EPI_SILU_MUL, rowmap(P.act, I));
+  g.xf = xf_norm(w.post_norm, k.rms_eps);
+  GemmArgs d = gemm_args(c, P.ntok, H, I, rowmap(P.act, I), w.down, EPI_RES, P.hm);
   tp_residual(c, d, P.hm);
   // prefill: SiLU*up written MFMA-fragment-packed for the down projection when
   // both take the 256 x 256 tile (16K rows: down 449 -> 388 us)
@@ -1678,8 +1673,8 @@ static int lm_end(vv_ctx* c, LmPass& P, int nout, const int* out_idx, void* hidd
   if (nout <= 0) return 0;
   const vv_config& k = c->cfg;
   // gather the output rows + final norm + the valid-id lm_head rows, one launch
-  KCHK(launch_final_head(nout, k.hidden, P.h, out_idx, W(c, "lm.norm"), k.rms_eps, (bf16*)hidden_out,
-                         W(c, "lm.lm_head"), (const int*)c->valid_ids.p, logits_out ? c->n_valid : 0, logits_out,
+  KCHK(launch_final_head(nout, k.hidden, P.h, out_idx, c->lm.norm, k.rms_eps, (bf16*)hidden_out,
+                         c->lm.lm_head, (const int*)c->valid_ids.p, logits_out ? c->n_valid : 0, logits_out,
                          st));
   return 0;
 }
@@ -1916,7 +1911,7 @@ static int head_begin(vv_ctx* c, int n, const void* pos_h, const void* neg_h, He
   // Infinity Cache (256 MB) across the S steps.  VibeVoice-Large's (925 MB per
   // step; 231 MB per rank at TP = 4) stream non-temporal like the LM's
   h.keep = (size_t)L * 3 * F * H * sizeof(bf16) <= (192ull << 20) && !(c->head_tp && c->tp_size > 1);
-  CHK(gemm(c, gemm_args(c, R, H, H, rowmap(h.cond, H), W(c, "head.cond_w"), EPI_STORE, rowmap(h.condp, H)), st));
+  CHK(gemm(c, gemm_args(c, R, H, H, rowmap(h.cond, H), c->head.cond, EPI_STORE, rowmap(h.condp, H)), st));
   return 0;
 }
 
@@ -1933,7 +1928,7 @@ static int head_mods(vv_ctx* c, const HeadRun& h, int s, hipStream_t st) {
   if (s % HEAD_SC) return 0;
   const int H = c->cfg.hidden, sc = std::min(HEAD_SC, c->steps - s);
   KCHK(launch_head_cond(sc, h.R, H, h.condp, (const bf16*)c->temb.p + (size_t)s * H, h.sa, st));
-  CHK(gemm(c, gemm_args(c, sc * h.R, (int)h.MODW, H, rowmap(h.sa, H), W(c, "head.ada_w"), EPI_STORE,
+  CHK(gemm(c, gemm_args(c, sc * h.R, (int)h.MODW, H, rowmap(h.sa, H), c->head.ada, EPI_STORE,
                         rowmap(h.mods, h.MODW)), st));
   return 0;
 }
@@ -1976,7 +1971,7 @@ static int head_noisy(vv_ctx* c, const HeadRun& h, const void* x_io, hipStream_t
   if (m16_pre(c, h.R)) {   // + the row partials layer 0's distributed A side reads
     HeadNoisyArgs a;
     a.lat = (const bf16*)x_io;
-    a.w = (const bf16*)W(c, "head.noisy_w");
+    a.w = c->head.noisy;
     a.x = (bf16*)h.xh;
     a.ssp = (float*)c->m16_buf.p;
     a.n = h.n;
@@ -1986,7 +1981,7 @@ static int head_noisy(vv_ctx* c, const HeadRun& h, const void* x_io, hipStream_t
     KCHK(launch_head_noisy16(a, st));
     return 0;
   }
-  return head_gemm(c, h, gemm_args(c, h.R, H, D, rowmap(x_io, D, h.n, 0), W(c, "head.noisy_w"), EPI_STORE, h.xh_m),
+  return head_gemm(c, h, gemm_args(c, h.R, H, D, rowmap(x_io, D, h.n, 0), c->head.noisy, EPI_STORE, h.xh_m),
                    st);
 }
 
@@ -2005,12 +2000,12 @@ extern "C" int vv_head_m16_active(vv_ctx* c, int n) {
 static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, F = k.head_ffn;
-  const std::string p = "head." + std::to_string(l);
+  const HeadLayerW& w = c->headw[l];
   const bf16* mod = h.mods + (size_t)(s % HEAD_SC) * h.R * h.MODW;
   const int o = 3 * H * l;
   // modulate(norm(x), shift, scale) fused into gate|up's A load
-  GemmArgs g = gemm_args(c, h.R, 2 * F, H, h.xh_m, W(c, p + ".gu_w"), EPI_SILU_MUL, rowmap(h.act, F));
-  g.xf = xf_norm(W(c, p + ".norm"), k.head_eps, mod, h.MODW, o, o + H);
+  GemmArgs g = gemm_args(c, h.R, 2 * F, H, h.xh_m, w.gu, EPI_SILU_MUL, rowmap(h.act, F));
+  g.xf = xf_norm(w.norm, k.head_eps, mod, h.MODW, o, o + H);
   const bool partial = c->head_tp && c->tp_size > 1 && c->tp_rank > 0;
   if (m16_on(c, h.R)) {
     // 2n <= 16 rows, GEMV layout: one launch with two grid-wide waits (head_m16.hip)
@@ -2026,9 +2021,9 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
     a.gate_off = o + 2 * H;
     a.R = h.R;
     a.eps = k.head_eps;
-    a.nw = W(c, p + ".norm");
-    a.gu = W(c, p + ".gu_w");
-    a.dn = W(c, p + ".down_w");
+    a.nw = w.norm;
+    a.gu = w.gu;
+    a.dn = w.down;
     a.act = h.act;
     a.sync = (unsigned*)c->hf_sync.p;
     a.err = err_word(c);
@@ -2047,7 +2042,7 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
     FAIL("diffusion head: " + std::to_string(h.R) + " rows need the GEMV layout (head.<l>.gu_w / down_w), which this "
          "engine did not bind");
   CHK(head_gemm(c, h, g, st));
-  g = gemm_args(c, h.R, H, F, rowmap(h.act, F), W(c, p + ".down_w"), EPI_RES, h.xh_m);
+  g = gemm_args(c, h.R, H, F, rowmap(h.act, F), w.down, EPI_RES, h.xh_m);
   g.epi.res = partial ? rowmap(c->zero_rows.p, H) : h.xh_m;
   g.epi.gate = rowmap(mod + o + 2 * H, h.MODW);
   return head_gemm(c, h, g, st);
@@ -2063,7 +2058,7 @@ static int head_final(vv_ctx* c, const HeadRun& h, int s, void* x_io, float cfg_
   e.cfg = cfg_scale;
   // sde-dpmsolver++: this step's [2n, D] fp32 draw; rows [0, n) update the live latents
   const float* zs = sde_noise ? sde_noise + (size_t)s * h.R * D : nullptr;
-  GemmArgs g = gemm_args(c, h.R, D, H, h.xh_m, W(c, "head.final_w"), EPI_STORE, rowmap(h.v, D));
+  GemmArgs g = gemm_args(c, h.R, D, H, h.xh_m, c->head.final, EPI_STORE, rowmap(h.v, D));
   g.xf = xf_norm(nullptr, k.head_eps, mod, h.MODW, 3 * H * L, 3 * H * L + H);
   if (h.R <= 16) {
     g.epi.kind = EPI_CFG_DPM;
@@ -2140,7 +2135,7 @@ static int head_fin(vv_ctx* c, const HeadRun& h, int s, const bf16* lat, bf16* l
   a.ldmod = h.MODW;
   a.x = h.xh;
   a.mod = h.mods + (size_t)(s % HEAD_SC) * h.R * h.MODW;
-  a.fw = W(c, "head.final_w");
+  a.fw = c->head.final;
   a.k = c->coef[s];
   a.k.cfg = cfg_scale;
   a.lat = lat;
@@ -2148,7 +2143,7 @@ static int head_fin(vv_ctx* c, const HeadRun& h, int s, const bf16* lat, bf16* l
   a.m1 = m1;
   a.m1_out = m1_out;
   a.noise = sde_noise ? sde_noise + (size_t)s * h.R * D : nullptr;
-  a.nw = W(c, "head.noisy_w");
+  a.nw = c->head.noisy;
   a.xo = xo;
   a.ssp = m16_pre(c, h.R) ? (float*)c->m16_buf.p : nullptr;   // (layer 0's distributed A side at > 4 rows)
   KCHK(launch_head_fin(a, st));
@@ -2239,17 +2234,16 @@ int vv_diffusion_sample_group(int nr, vv_ctx* const* ctxs, int n, const void* po
   return 0;
 }
 
-static int connector(vv_ctx* c, const char* which, int n, int din, RowMap x, RowMap out, const RowMap* res,
+static int connector(vv_ctx* c, const ConnW& w, int n, int din, RowMap x, RowMap out, const RowMap* res,
                      hipStream_t st) {
   const int H = c->cfg.hidden;
-  const std::string p(which);
   bf16* t1 = (bf16*)c->codec_ws.p;
   bf16* t2 = t1 + (size_t)c->cfg.max_batch * H;
   RowMap t1m = rowmap(t1, H), t2m = rowmap(t2, H);
-  CHK(gemm(c, gemm_args(c, n, H, din, x, W(c, p + ".fc1_w"), EPI_STORE, t1m, W(c, p + ".fc1_b")), st));
+  CHK(gemm(c, gemm_args(c, n, H, din, x, w.fc1_w, EPI_STORE, t1m, w.fc1_b), st));
   // LlamaRMSNorm(eps=1e-6) (modeling_vibevoice.py:62) fused into fc2's A load
-  GemmArgs g = gemm_args(c, n, H, H, t1m, W(c, p + ".fc2_w"), res ? EPI_RES : EPI_STORE, out, W(c, p + ".fc2_b"));
-  g.xf = xf_norm(W(c, p + ".norm"), 1e-6f);
+  GemmArgs g = gemm_args(c, n, H, H, t1m, w.fc2_w, res ? EPI_RES : EPI_STORE, out, w.fc2_b);
+  g.xf = xf_norm(w.norm, 1e-6f);
   if (res) g.epi.res = *res;
   CHK(gemm(c, g, st));
   return 0;
@@ -2257,12 +2251,13 @@ static int connector(vv_ctx* c, const char* which, int n, int din, RowMap x, Row
 
 int vv_connector(vv_ctx* c, int which, int n, const void* x, void* out, vv_stream vst) {
   hipStream_t st = (hipStream_t)vst;
+  if (!c->finalized) FAIL("vv_connector before vv_finalize");
   const int H = c->cfg.hidden;
   const int din = which == 0 ? c->cfg.latent_dim : c->cfg.semantic_dim;
   // chunk rows through the max_batch-sized connector workspace
   for (int r0 = 0; r0 < n; r0 += c->cfg.max_batch) {
     const int m = std::min(c->cfg.max_batch, n - r0);
-    CHK(connector(c, which == 0 ? "conn.ac" : "conn.se", m, din, rowmap((const bf16*)x + (size_t)r0 * din, din),
+    CHK(connector(c, which == 0 ? c->conn_ac : c->conn_se, m, din, rowmap((const bf16*)x + (size_t)r0 * din, din),
                   rowmap((bf16*)out + (size_t)r0 * H, H), nullptr, st));
   }
   return 0;
@@ -2279,7 +2274,7 @@ int vv_codec_step(vv_ctx* c, int n, const int* slots, const void* latent, void* 
   ConvNet& sn = c->sem;
   const int hop = dn.T[dn.nst - 1];
   // decoder input: latent / scaling - bias  (modeling_vibevoice_inference.py:651)
-  KCHK(launch_latent_to_dec(n, D, (const bf16*)latent, W(c, "speech_scaling_factor"), W(c, "speech_bias_factor"),
+  KCHK(launch_latent_to_dec(n, D, (const bf16*)latent, c->scaling, c->bias,
                             buf_in_rows(dn.stem, 1, slots), st));
   // decoder -> audio chunk (also written as the semantic encoder's input rows)
   CHK(convnet_run(c, dn, n, slots, rowmap(audio_out, 1, hop, hop), buf_in_rows(sn.stem, hop, slots), st));
@@ -2292,9 +2287,9 @@ int vv_codec_step(vv_ctx* c, int n, const int* slots, const void* latent, void* 
   if (embeds_out) {
     bf16* ac = (bf16*)c->codec_ws.p + (size_t)c->cfg.max_batch * 3 * H;
     RowMap acm = rowmap(ac, H);
-    CHK(connector(c, "conn.ac", n, D, rowmap(latent, D), acm, nullptr, st));
+    CHK(connector(c, c->conn_ac, n, D, rowmap(latent, D), acm, nullptr, st));
     RowMap outm = rowmap(embeds_out, H, 1, H, embed_rows);
-    CHK(connector(c, "conn.se", n, S, rowmap(sem, S), outm, &acm, st));
+    CHK(connector(c, c->conn_se, n, S, rowmap(sem, S), outm, &acm, st));
   }
   return 0;
 }
@@ -2359,10 +2354,10 @@ int vv_codec_reset_net(vv_ctx* c, int net, int n, const int* slots, vv_stream vs
 // the input, zeroed per call) is the reference's non-streaming extra padding
 // (modular_vibevoice_tokenizer.py:127-133, :393-408), so a clip that ends in a
 // partial frame gives ceil(L / hop) frames as the reference does.
-static int encode_nonstreaming(vv_ctx* c, ConvNet& net, const char* wp, int nf, int out_ch, int nv, int L,
-                               const void* audio, void* out, hipStream_t st) {
-  if (net.slots != nv || net.T0 != L || net.wp != wp) {
-    convnet_shape(c, net, false, wp, nf, 1, out_ch, L, nv);
+static int encode_nonstreaming(vv_ctx* c, ConvNet& net, int nf, int out_ch, int nv, int L, const void* audio, void* out,
+                               hipStream_t st) {
+  if (net.slots != nv || net.T0 != L) {
+    convnet_shape(c, net, false, net.wp, nf, 1, out_ch, L, nv);   // (the channels, so the weights, as vv_finalize's)
     CHK(convnet_alloc(net, 7));
   } else {
     HIPCHK(hipMemsetAsync(net.state.p, 0, net.state.bytes, st));
@@ -2381,24 +2376,25 @@ static int encode_nonstreaming(vv_ctx* c, ConvNet& net, const char* wp, int nf, 
 }
 
 int vv_acoustic_encode(vv_ctx* c, int nv, int L, const void* audio, void* mean_out, vv_stream vst) {
-  if (!c->w.count("aenc.stem_w")) FAIL("acoustic encoder weights not bound");
+  if (!c->finalized) FAIL("vv_acoustic_encode before vv_finalize");
+  if (!c->has_aenc) FAIL("acoustic encoder weights not bound");
   if (nv <= 0 || L <= 0) return 0;
-  return encode_nonstreaming(c, c->aenc, "aenc", c->cfg.ac_enc_n_filters, c->cfg.latent_dim, nv, L, audio, mean_out,
+  return encode_nonstreaming(c, c->aenc, c->cfg.ac_enc_n_filters, c->cfg.latent_dim, nv, L, audio, mean_out,
                              (hipStream_t)vst);
 }
 
 int vv_semantic_encode(vv_ctx* c, int nv, int L, const void* audio, void* mean_out, vv_stream vst) {
   if (!c->finalized) FAIL("vv_semantic_encode before vv_finalize");
   if (nv <= 0 || L <= 0) return 0;
-  return encode_nonstreaming(c, c->senc, "sem", c->cfg.sem_n_filters, c->cfg.semantic_dim, nv, L, audio, mean_out,
+  return encode_nonstreaming(c, c->senc, c->cfg.sem_n_filters, c->cfg.semantic_dim, nv, L, audio, mean_out,
                              (hipStream_t)vst);
 }
 
 int vv_vae_features(vv_ctx* c, int nv, int frames, const void* mean, const void* stdv, const void* noise, void* feat,
                     vv_stream vst) {
+  if (!c->finalized) FAIL("vv_vae_features before vv_finalize");
   KCHK(launch_vae_features(nv * frames, c->cfg.latent_dim, frames, (const bf16*)mean, (const bf16*)stdv,
-                           (const bf16*)noise, W(c, "speech_scaling_factor"), W(c, "speech_bias_factor"),
-                           (bf16*)feat, (hipStream_t)vst));
+                           (const bf16*)noise, c->scaling, c->bias, (bf16*)feat, (hipStream_t)vst));
   return 0;
 }
 

@@ -335,14 +335,17 @@ bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys);
 size_t lm_attn_part_floats(int R, int keys);
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st);
 
-// A whole codec stage of Block1Ds for one sample in ONE persistent launch
-// (codec_stage.hip): C = 2,048 at T = 1, C = 1,024 at T = 2 or 8.
-struct CodecStageBlock {
-  const bf16 *norm, *dw_w, *dw_b, *gamma, *ffn_norm;   // mixer norm, depthwise conv [C][7] + bias, layer scale, FFN norm
-  const bf16 *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ffn_gamma;   // MFMA-packed fc1 [4C][C], fc2 [C][4C]
-  bf16* mix;                // the block's conv buffer (history rows 0 .. ctx-1, new row ctx)
+// One codec Block1D's operands, as the one-launch stage kernels take them (b[] below)
+// and as the engine keeps them per block (resolved once, at vv_finalize).
+struct Block1D {
+  const bf16 *norm, *dw_w, *dw_b, *gamma, *ffn_norm;      // mixer norm, depthwise conv [C][7] + bias, layer scale, FFN norm
+  const bf16 *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ffn_gamma;  // MFMA-packed fc1 [4C][C], fc2 [C][4C]
+  bf16* mix;                // the block's conv buffer (ctx history rows, then this frame's rows)
   long long mix_sB;         // elements per slot
 };
+
+// A whole codec stage of Block1Ds for one sample in ONE persistent launch
+// (codec_stage.hip): C = 2,048 at T = 1, C = 1,024 at T = 2 or 8.
 struct CodecStageArgs {
   int depth, ctx;
   int C, M;                 // channels; rows = T (one sample)
@@ -352,7 +355,7 @@ struct CodecStageArgs {
   bf16* xe;                 // [M][C] block outputs between blocks (written through)
   bf16* h;                  // [M][4C] hidden rows (written through)
   RowMap out;               // the last block's output rows
-  CodecStageBlock b[8];
+  Block1D b[8];
   unsigned* sync;           // cs_sync (sync_layout.h: shard lines, generation pk::GEN_CODEC_STAGE)
   unsigned* err;            // set to 1 when a grid wait gave up
   unsigned long long* stamps;   // diagnostics: [G][64] s_memrealtime per phase, or nullptr
@@ -369,12 +372,6 @@ int launch_codec_stage(const CodecStageArgs& a, hipStream_t st);
 // Block1Ds and (decoder) the head conv.
 enum { CT_PRE_NONE = 0, CT_PRE_CONVT = 1, CT_PRE_SCONV = 2, CT_PRE_STEM = 3 };
 enum { CT_POST_NONE = 0, CT_POST_HEAD = 1 };
-struct CodecTileBlock {
-  const bf16 *norm, *dw_w, *dw_b, *gamma, *ffn_norm;      // mixer norm, depthwise conv [C][7] + bias, layer scale, FFN norm
-  const bf16 *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ffn_gamma;  // MFMA-packed fc1 [4C][C], fc2 [C][4C]
-  bf16* mix;                // the block's conv buffer (6 history rows, then this frame's rows)
-  long long mix_sB;         // elements per slot
-};
 struct CodecTileArgs {
   int n, T, depth;          // samples, rows per sample (the stage's), blocks (3)
   float eps;
@@ -384,7 +381,7 @@ struct CodecTileArgs {
   long long pre_sB;
   const bf16* pre_w;        // convT [2C][4C] / sconv [C][2C] MFMA-packed; stem [C][7]
   const bf16* pre_b;        // convT [2C] (repeated per phase) / sconv, stem [C]
-  CodecTileBlock b[3];
+  Block1D b[3];
   RowMap out;               // CT_POST_NONE: stage output rows (row = sample * T + t)
   const bf16* head_w;       // CT_POST_HEAD: [7][C], bias [1]
   const bf16* head_b;
@@ -405,7 +402,7 @@ struct CodecWideArgs {
   float eps;
   const int* slots;
   const bf16* x;            // stage input rows [n][T][C]
-  CodecTileBlock b[3];
+  Block1D b[3];
   RowMap out;               // stage output rows (row = sample * T + t)
   unsigned* sync;           // this C's half of cw_sync (sync_layout.h): one line per cluster (n x tiles), monotonic counters
   unsigned* err;            // set to 1 when a wait gave up
