@@ -56,27 +56,9 @@ DEV int row_chunk(const AttnArgs& a, int len) {
 
 DEV f32x4 amfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
-// max / sum over the 16 lanes of a DPP row (one MFMA tile column group) with
-// row-local DPP moves on the VALU: quad xor 1, quad xor 2, half-row mirror,
-// row mirror (a butterfly: every lane ends with the whole row's value; each step
-// adds a lane pair in both orders, so all lanes agree bit for bit).  Four
-// __shfl_xor were four dependent ds_bpermute LDS round trips.
-template <int CTRL>
-DEV float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-DEV float row16_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  return fmaxf(v, dpp_f<0x140>(v));
-}
-DEV float row16_sum(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  return v + dpp_f<0x140>(v);
-}
+// The softmax row max / sum over an MFMA tile's 16-lane column group are
+// common.h's row16_max / row16_sum (row-local DPP moves on the VALU; four
+// __shfl_xor were four dependent ds_bpermute LDS round trips).
 
 DEV void astamp(const AttnArgs& a, int which) {
   if (a.stamps && threadIdx.x == 0) {

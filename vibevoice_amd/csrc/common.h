@@ -102,6 +102,23 @@ DEV float group_sum(float v) {
   return v;
 }
 DEV float wave_sum(float v) { return group_sum<64>(v); }
+// max / sum over the 16 lanes of a DPP row (one MFMA tile column group): the
+// same four row-local butterflies, every lane ends with the row's value
+DEV float row16_max(float v) {
+  v = fmaxf(v, dpp_mov<0xB1>(v));
+  v = fmaxf(v, dpp_mov<0x4E>(v));
+  v = fmaxf(v, dpp_mov<0x141>(v));
+  return fmaxf(v, dpp_mov<0x140>(v));
+}
+DEV float row16_sum(float v) { return group_sum<16>(v); }
+// whole-wave max (every lane gets it), wave_sum's steps
+DEV float wave_max(float v) {
+  v = row16_max(v);
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
 // runtime group width (a wave-uniform power of two <= 64; every lane of a group active)
 DEV float group_sum_n(float v, int n) {
   switch (n) {

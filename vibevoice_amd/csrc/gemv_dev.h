@@ -86,6 +86,29 @@ DEV void row_inv(const GemmArgs& a, int m0, int nrows, float* inv_s, int wave, i
   row_inv<MemPlain>(a.a, a.M, a.K, a.xf.eps, m0, nrows, inv_s, wave, NW, lane);
 }
 
+// XF_NORM's rounding chain: RMSNorm, its weight, adaLN modulate -- one torch op,
+// one rounding each.  The one place each step is written:
+DEV float norm_x(bf16 x, float inv) { return rb(bf(x) * inv); }
+DEV float norm_w(float t, bf16 w) { return rb(t * bf(w)); }
+DEV float norm_mod(float t, bf16 sc, bf16 sh) { return rb(rb(t * rb(1.0f + bf(sc))) + bf(sh)); }
+// the chain on 8 values of a row with inverse RMS inv, the weight / modulation
+// present at compile time (an absent operand is never read: pass anything).
+// xform<XF_NORM> below runs the same steps under GemmArgs' runtime tests: routed
+// through norm8 (flags as arguments, or a four-way dispatch) k_gemv and k_gemv_w8
+// compiled to other code.
+template <bool HAS_W, bool HAS_MOD>
+DEV bf16x8 norm8(bf16x8 x, float inv, bf16x8 w, bf16x8 sc, bf16x8 sh) {
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float t = norm_x(x[j], inv);
+    if (HAS_W) t = norm_w(t, w[j]);
+    if (HAS_MOD) t = norm_mod(t, sc[j], sh[j]);
+    o[j] = tobf(t);
+  }
+  return o;
+}
+
 template <int XF, class MP = MemPlain>
 DEV bf16x8 xform(const GemmArgs& a, bf16x8 x, int m, int k, float inv) {
   bf16x8 o;
@@ -99,9 +122,9 @@ DEV bf16x8 xform(const GemmArgs& a, bf16x8 x, int m, int k, float inv) {
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = rb(bf(x[j]) * inv);
-      if (a.xf.w) t = rb(t * bf(wv[j]));
-      if (md) t = rb(rb(t * rb(1.0f + bf(sc[j]))) + bf(sh[j]));
+      float t = norm_x(x[j], inv);
+      if (a.xf.w) t = norm_w(t, wv[j]);
+      if (md) t = norm_mod(t, sc[j], sh[j]);
       o[j] = tobf(t);
     }
   } else if (XF == XF_SILU_ADD) {

@@ -14,7 +14,7 @@
 // new latents and DPM history; the caller double-buffers them and the state
 // rows (a launch reads lat / m1 / x and writes lat_out / m1_out / xo: no
 // workgroup may overwrite what another has yet to read).
-// Arithmetic: xform<XF_NORM>'s (no norm weight, adaLN modulate), epi_dpm's
+// Arithmetic: persist_dev.h hl_rows_norm (no norm weight, adaLN modulate), epi_dpm's
 // term for term, EPI_STORE for noisy; MFMA sums in another order than the GEMV
 // kernels' (tests: within bf16 of them).
 #include "persist_dev.h"
@@ -83,24 +83,8 @@ __global__ void __launch_bounds__(hf::NT) k_head_fin(HeadFinArgs a) {
     if (ln == 0) inv_s[m] = rsqrtf(ss / (float)H + a.eps);
   }
   __syncthreads();
-  for (int e = hl_vopaque((int)threadIdx.x); e < 16 * (H / 8); e += NT) {   // xform<XF_NORM> (modulate), in place
-    const int m = e / (H / 8), c = e - m * (H / 8);
-    bf16x8 o;
-    if (m < R) {
-      const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8);
-      const bf16x8 sh = *(const bf16x8*)(sh_s + m * H + c * 8), sc = *(const bf16x8*)(sc_s + m * H + c * 8);
-      const float inv = inv_s[m];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float t = rb(bf(xv[j]) * inv);
-        t = rb(rb(t * rb(1.0f + bf(sc[j]))) + bf(sh[j]));
-        o[j] = tobf(t);
-      }
-    } else {
-      o = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-    }
-    *(bf16x8*)(xs + m * XST + c * 8) = o;
-  }
+  // (rows R..15 zeroed: the final layer's B operand reads all 16)
+  hl_rows_norm<H, false, true, true>(xs, XST, R, nullptr, sc_s, sh_s, H, inv_s, hl_vopaque((int)threadIdx.x), NT);
   __syncthreads();
   // ---- the final layer: D[n][m], A = the weight tile, B = the rows; 8 K slices -> LDS
 #pragma unroll

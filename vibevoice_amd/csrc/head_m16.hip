@@ -23,8 +23,8 @@
 //     launch's end publishes them).
 // Weights are read with the default cache policy: the head's 170 MB are read S
 // times per token and stay in the Infinity Cache (gemv_dev.h ldw<KEEP>).
-// Arithmetic: xform<XF_NORM>'s rounding points and k_rmsnorm's row order for
-// the norm; the GEMM sums are fp32 MFMA sums in another order than the GEMV
+// Arithmetic: persist_dev.h hl_rows_norm (gemv_dev.h norm8) and hl_silu_up,
+// k_rmsnorm's row order for the norm; the GEMM sums are fp32 MFMA sums in another order than the GEMV
 // kernels', so the layer is within bf16 of the two-launch path, not bitwise
 // (tests/test_gpu_head.py).
 #include "persist_dev.h"
@@ -93,9 +93,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
   // LDS, 8 down partials in LDS, 9 end (owners); 10 A side landed (wave 7),
   // 11 gate / x columns landed (control wave), 12 / 13 wave 0's norm / transform
   // loop done (before the barrier)
-  auto stamp = [&](int k, bool by_ctl) {
-    if (a.stamps && threadIdx.x == (by_ctl ? NTC : 0)) a.stamps[w * 16 + k] = __builtin_amdgcn_s_memrealtime();
-  };
+  auto stamp = [&](int k, bool by_ctl) { hl_stamp(a.stamps, w, k, by_ctl ? NTC : 0); };
   stamp(0, true);
   if (ctl) __builtin_amdgcn_s_setprio(3);
   if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_HEAD_M16);
@@ -175,7 +173,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
   if (a.pre) {
     // the distributed transform: owner rows' inverse RMS from the 192 partials
     // (fixed order: 4 lanes per row, 48 partials each, then pairwise), its 8
-    // columns modulated (xform<XF_NORM>'s rounding points) and written through
+    // columns modulated (norm8) and written through
     if (ctl && owner) {
       const int m = lane >> 2, q = lane & 3;
       const float* ps = (const float*)sh_s + m * NOWN + q * (NOWN / 4);
@@ -188,14 +186,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
       if (lane < R) {
         const bf16x8 xv = *(const bf16x8*)(xraw_s + lane * 8), wv = *(const bf16x8*)nw_s;
         const bf16x8 scv = *(const bf16x8*)(sc_s + lane * 8), shv = *(const bf16x8*)(sc_s + RMAX * 8 + lane * 8);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float t = rb(bf(xv[j]) * invm);
-          t = rb(t * bf(wv[j]));
-          t = rb(rb(t * rb(1.0f + bf(scv[j]))) + bf(shv[j]));
-          o[j] = tobf(t);
-        }
+        const bf16x8 o = norm8<true, true>(xv, invm, wv, scv, shv);
         bf16* dst = hl_opaque(a.xt) + (long long)lane * H + col0;
         MemWT::st8(dst, __builtin_shufflevector(o, o, 0, 1, 2, 3));
         MemWT::st8(dst + 4, __builtin_shufflevector(o, o, 4, 5, 6, 7));
@@ -230,22 +221,8 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
   if (wave == 0 && a.stamps && lane == 0) a.stamps[w * 16 + 12] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();
   stamp(2, true);
-  // xform<XF_NORM>, in place, rows < R (rows >= R stay unset: their MFMA rows are never read)
-  for (int e = hl_vopaque((int)threadIdx.x); e < R * NCH; e += NT) {
-    const int m = e / NCH, c = e - m * NCH;
-    bf16x8 o;
-    const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8), wv = *(const bf16x8*)(nw_s + c * 8);
-    const bf16x8 shv = *(const bf16x8*)(sh_s + e * 8), scv = *(const bf16x8*)(sc_s + e * 8);
-    const float inv = inv_s[m];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = rb(bf(xv[j]) * inv);
-      t = rb(t * bf(wv[j]));
-      t = rb(rb(t * rb(1.0f + bf(scv[j]))) + bf(shv[j]));
-      o[j] = tobf(t);
-    }
-    *(bf16x8*)(xs + m * XST + c * 8) = o;
-  }
+  // rows < R (rows >= R stay unset: their MFMA rows are never read)
+  hl_rows_norm<H, true, true>(xs, XST, R, nw_s, sc_s, sh_s, H, inv_s, hl_vopaque((int)threadIdx.x), NT);
   if (wave == 0 && a.stamps && lane == 0) a.stamps[w * 16 + 13] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();
   stamp(3, true);
@@ -278,7 +255,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
       g += red1[(j * 8 + v) * 256 + (c + 16 * (m >> 2)) * 4 + (m & 3)];
       u += red1[(j * 8 + v) * 256 + (c + 8 + 16 * (m >> 2)) * 4 + (m & 3)];
     }
-    su_s[e] = tobf(rb(silu_f(rb(g))) * rb(u));
+    su_s[e] = hl_silu_up(g, u);
   }
   __syncthreads();
   stamp(5, true);

@@ -29,19 +29,6 @@ namespace {
 constexpr int KQ_WAVES = 4;
 constexpr int E_MIN = -100;   // weights.py _E_MIN
 
-// max over the wave (every lane gets it): the DPP butterflies of a 16-lane row,
-// then gfx950's v_permlane16_swap / v_permlane32_swap across the rows (common.h group_sum)
-DEV float wave_max(float v) {
-  v = fmaxf(v, dpp_mov<0xB1>(v));
-  v = fmaxf(v, dpp_mov<0x4E>(v));
-  v = fmaxf(v, dpp_mov<0x141>(v));
-  v = fmaxf(v, dpp_mov<0x140>(v));
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
 // the row exponent of amax (>= 0, finite): amax = m * 2^x, m in [0.5, 1), and
 // 448 * 2^e = 0.875 * 2^(e + 9), so e = x - 9 when m <= 0.875, else x - 8
 DEV int row_exp(float amax) {

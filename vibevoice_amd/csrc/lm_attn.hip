@@ -51,37 +51,7 @@ static_assert(SM + SM_B <= 160 * 1024, "lm attn LDS");
 static_assert(GRID == pk::G, "grid waits: 256 arrivals per wait");
 }  // namespace la
 
-DEV void la_stamp(const LmAttnArgs& a, int k) {
-  if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 16 + k] = __builtin_amdgcn_s_memrealtime();
-}
-
-template <int CTRL>
-DEV float la_dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-DEV float la_max16(float v) {   // max over the 16 lanes of a DPP row (attention.hip row16_max)
-  v = fmaxf(v, la_dppf<0xB1>(v));
-  v = fmaxf(v, la_dppf<0x4E>(v));
-  v = fmaxf(v, la_dppf<0x141>(v));
-  return fmaxf(v, la_dppf<0x140>(v));
-}
-DEV float la_sum16(float v) {
-  v += la_dppf<0xB1>(v);
-  v += la_dppf<0x4E>(v);
-  v += la_dppf<0x141>(v);
-  return v + la_dppf<0x140>(v);
-}
-
-DEV float wave_max(float v) {   // every lane ends with the wave's max (wave_sum's steps)
-  v = fmaxf(v, la_dppf<0xB1>(v));
-  v = fmaxf(v, la_dppf<0x4E>(v));
-  v = fmaxf(v, la_dppf<0x141>(v));
-  v = fmaxf(v, la_dppf<0x140>(v));
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
+DEV void la_stamp(const LmAttnArgs& a, int k) { hl_stamp(a.stamps, blockIdx.x, k, 0); }
 
 __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   using namespace la;
@@ -168,16 +138,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
       if (ln == 0) inv_s[m] = rsqrtf(ss / (float)H + a.eps);
     }
     __syncthreads();
-    for (int e = hl_vopaque((int)threadIdx.x); e < mr * (H / 8); e += NT) {   // xform<XF_NORM>, in place
-      const int m = e / (H / 8), c = e - m * (H / 8);
-      const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8);
-      const bf16x8 wv = *(const bf16x8*)(nw_s + c * 8);
-      const float inv = inv_s[m];
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = tobf(rb(rb(bf(xv[j]) * inv) * bf(wv[j])));
-      *(bf16x8*)(xs + m * XST + c * 8) = o;
-    }
+    hl_rows_norm<H, true, false>(xs, XST, mr, nw_s, nullptr, nullptr, 0, inv_s, hl_vopaque((int)threadIdx.x), NT);
     __syncthreads();
     // D[n][m]: A = the weight tile (row n = lane & 15), B = the A rows (column m)
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -300,10 +261,10 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     for (int i = 0; i < 4; ++i) {
       const float s0 = c0 + r16 < w1 ? sacc[0][i] * a.scale : -INFINITY;
       const float s1 = c0 + 16 + r16 < w1 ? sacc[1][i] * a.scale : -INFINITY;
-      const float mx = la_max16(fmaxf(s0, s1));
+      const float mx = row16_max(fmaxf(s0, s1));
       pp[0][i] = __expf(s0 - mx);
       pp[1][i] = __expf(s1 - mx);
-      lv[i] = la_sum16(pp[0][i] + pp[1][i]);
+      lv[i] = row16_sum(pp[0][i] + pp[1][i]);
       mv[i] = mx;
     }
     bf16* ptw = pt + wave * 512;

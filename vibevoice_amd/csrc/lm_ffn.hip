@@ -19,8 +19,8 @@
 //     down tile over all 8,960 k, 140 KB: 18 k-blocks per wave in registers, 17
 //     by DMA into LDS, only this workgroup's 8 rows of each block); issued after
 //     SiLU * up so they stream through the hand-off; MFMA; residual.
-// Arithmetic: xform<XF_NORM>'s rounding points (norm weight, no modulation), the
-// residual as epi_row8's EPI_RES; the GEMM sums are fp32 MFMA sums in another
+// Arithmetic: persist_dev.h hl_rows_norm (norm weight, no modulation) and
+// hl_silu_up, the residual as epi_row8's EPI_RES; the GEMM sums are fp32 MFMA sums in another
 // order than the GEMV kernels' (tests/test_gpu_lm.py: within bf16 of them).
 #include "persist_dev.h"
 
@@ -87,9 +87,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
   if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_LM_FFN);
   // diagnostics (k_lm_ffn16's numbering): 0 start, 1 A side in LDS, 2 normalised, 3 gate|up
   // products, 4 SiLU * up, 5 hand-off released, 6 act rows + down weights landed, 9 end
-  auto stamp = [&](int k) {
-    if (a.stamps && threadIdx.x == 0) a.stamps[w * 16 + k] = __builtin_amdgcn_s_memrealtime();
-  };
+  auto stamp = [&](int k) { hl_stamp(a.stamps, w, k, 0); };
   stamp(0);
   auto issue_dn_lds = [&]() {
     // k-blocks [+18, +35) of the down weights by DMA into LDS slot wave, only
@@ -151,15 +149,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     if (ln == 0) inv_s[m] = rsqrtf(ss / (float)H + a.eps);
   }
   __syncthreads();
-  for (int e = hl_vopaque((int)threadIdx.x); e < R * NCH; e += NT) {   // xform<XF_NORM> (norm weight only), in place
-    const int m = e / NCH, c = e - m * NCH;
-    const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8), wv = *(const bf16x8*)(nw_s + c * 8);
-    const float inv = inv_s[m];
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = tobf(rb(rb(bf(xv[j]) * inv) * bf(wv[j])));
-    *(bf16x8*)(xs + m * XST + c * 8) = o;
-  }
+  hl_rows_norm<H, true, false>(xs, XST, R, nw_s, nullptr, nullptr, 0, inv_s, hl_vopaque((int)threadIdx.x), NT);
   __syncthreads();
   stamp(2);
   if (!ctl) {   // gate|up: D[row][tile row] over this wave's 6 k-blocks, per tile (rows >= R: never read)
@@ -192,7 +182,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
       g += red1[(j * 8 + v) * 256 + (c + 16 * (m >> 2)) * 4 + (m & 3)];
       u += red1[(j * 8 + v) * 256 + (c + 8 + 16 * (m >> 2)) * 4 + (m & 3)];
     }
-    su_s[(j * RMAX + m) * 8 + c] = tobf(rb(silu_f(rb(g))) * rb(u));
+    su_s[(j * RMAX + m) * 8 + c] = hl_silu_up(g, u);
   }
   __syncthreads();
   stamp(4);
@@ -293,7 +283,7 @@ int launch_lm_ffn(const LmFfnArgs& a, hipStream_t st) {
 //     waves, wave v = tile slot v / 2 over k-blocks [24 (v % 2), + 24)): at most
 //     452 KB per CU (stamps: both phases run at the per-CU ingest rate, so the
 //     owners' down phase must not sit on top of a 5th tile); the whole 16-row A side
-//     (48 KB) by LDS DMA, RMSNorm'd in place (xform<XF_NORM>'s rounding); MFMA;
+//     (48 KB) by LDS DMA, RMSNorm'd in place (hl_rows_norm); MFMA;
 //     the two K halves summed in order; SiLU * up -> the act columns, written
 //     through;
 //   * one grid wait;
@@ -352,9 +342,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   if (ctl) g0 = hl_base_gen(a.sync, pk::GEN_LM_FFN16);
   // diagnostics: 0 start, 1 A side in LDS, 2 A side normalised, 3 gate|up products, 4 SiLU * up,
   // 5 hand-off released, 6 act rows + down weights landed, 7 down products, 8 partial published, 9 end
-  auto stamp = [&](int k) {
-    if (a.stamps && threadIdx.x == 0) a.stamps[w * 16 + k] = __builtin_amdgcn_s_memrealtime();
-  };
+  auto stamp = [&](int k) { hl_stamp(a.stamps, w, k, 0); };
   stamp(0);
 
   bf16x8 wb[KH1];
@@ -389,15 +377,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
     if (ln == 0) inv_s[m] = rsqrtf(ss / (float)H + a.eps);
   }
   __syncthreads();
-  for (int e = hl_vopaque((int)threadIdx.x); e < RMAX * NCH; e += NT) {   // xform<XF_NORM> (norm weight only), in place
-    const int m = e / NCH, c = e - m * NCH;
-    const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8), wv = *(const bf16x8*)(nw_s + c * 8);
-    const float inv = inv_s[m];
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = tobf(rb(rb(bf(xv[j]) * inv) * bf(wv[j])));
-    *(bf16x8*)(xs + m * XST + c * 8) = o;
-  }
+  hl_rows_norm<H, true, false>(xs, XST, RMAX, nw_s, nullptr, nullptr, 0, inv_s, hl_vopaque((int)threadIdx.x), NT);
   __syncthreads();
   stamp(2);
   if (busy1) {   // gate|up tile t0 + js over this wave's K half
@@ -417,7 +397,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
     const int lg = (c + 16 * (m >> 2)) * 4 + (m & 3), lu = (c + 8 + 16 * (m >> 2)) * 4 + (m & 3);
     const float g = red[(j * 2) * 256 + lg] + red[(j * 2 + 1) * 256 + lg];
     const float u = red[(j * 2) * 256 + lu] + red[(j * 2 + 1) * 256 + lu];
-    su_s[(j * RMAX + m) * 8 + c] = tobf(rb(silu_f(rb(g))) * rb(u));
+    su_s[(j * RMAX + m) * 8 + c] = hl_silu_up(g, u);
   }
   __syncthreads();
   stamp(4);

@@ -63,6 +63,48 @@ DEV const bf16* hl_packed(const bf16* w, int K, int j, int k) {
   return w + ((long long)((j >> 4) * (K >> 5) + (k >> 5)) * 64 + (j & 15) + 16 * ((k & 31) >> 3)) * 8;
 }
 
+// diagnostic time stamp k of workgroup `slot` (16 words each), by thread tid_sel
+// (I: int or unsigned, as the kernel indexed before -- the extension of slot * 16 + k)
+template <class I>
+DEV void hl_stamp(unsigned long long* stamps, I slot, int k, int tid_sel) {
+  if (stamps && threadIdx.x == tid_sel) stamps[slot * 16 + k] = __builtin_amdgcn_s_memrealtime();
+}
+
+// ------------------------------------------------------------------ shared arithmetic
+// What the one-launch kernels (k_lm_ffn, k_lm_ffn16, k_head_m16, k_head_fin,
+// k_lm_attn) must compute to the GEMV path's bits, written once.  What stays per
+// kernel: the DMA issue order, the s_waitcnt counts, the LDS maps, and -- because
+// a helper compiled to other instructions there -- the row inverse-RMS loop
+// (gemv_dev.h row_inv's order), the D-tile index, the act store loop and the
+// workgroup-to-tile maps.
+//
+// xform<XF_NORM> over `rows` rows of H bf16 in LDS at stride XST, in place
+// (gemv_dev.h norm8): norm weight nw_s [H] (HAS_W), adaLN scale / shift rows sc_s /
+// sh_s at stride mod_stride (HAS_MOD), inverse RMS inv_s[m].  ZERO_TAIL: rows
+// [rows, 16) are zeroed (MFMA operand rows that are read).
+template <int H, bool HAS_W, bool HAS_MOD, bool ZERO_TAIL = false>
+DEV void hl_rows_norm(bf16* xs, int XST, int rows, const bf16* nw_s, const bf16* sc_s, const bf16* sh_s, int mod_stride,
+                      const float* inv_s, int tid, int NT) {
+  constexpr int NCH = H / 8;
+  for (int e = tid; e < (ZERO_TAIL ? 16 : rows) * NCH; e += NT) {
+    const int m = e / NCH, c = e - m * NCH;
+    bf16x8 o;
+    if (!ZERO_TAIL || m < rows) {
+      const bf16x8 xv = *(const bf16x8*)(xs + m * XST + c * 8);
+      const bf16x8 none = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};   // an absent operand (never read)
+      const bf16x8 wv = HAS_W ? *(const bf16x8*)(nw_s + c * 8) : none;
+      const bf16x8 shv = HAS_MOD ? *(const bf16x8*)(sh_s + m * mod_stride + c * 8) : none;
+      const bf16x8 scv = HAS_MOD ? *(const bf16x8*)(sc_s + m * mod_stride + c * 8) : none;
+      o = norm8<HAS_W, HAS_MOD>(xv, inv_s[m], wv, scv, shv);
+    } else {
+      o = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    *(bf16x8*)(xs + m * XST + c * 8) = o;
+  }
+}
+// SiLU(gate) * up from the fp32 sums (gemv_dev.h epi_silu8's rounding points)
+DEV bf16 hl_silu_up(float g, float u) { return tobf(rb(silu_f(rb(g))) * rb(u)); }
+
 // One grid-wide wait: arrival of this workgroup + poll until k waits of this
 // launch have completed.  Lane 0 of the control wave (or of the wave that made
 // the workgroup's last store), behind that wave's own s_waitcnt vmcnt(0).  The
