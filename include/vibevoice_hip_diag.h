@@ -35,6 +35,8 @@ int vv_kv_synthetic(vv_ctx* c, int n, const int* slots, int p0, int p1, unsigned
  * MFMA-packed order of vibevoice_amd/weights.py:mfma_pack (csrc/gemm.hip). */
 int vv_gemm_bf16(int M, int N, int K, const void* A, int64_t lda, const void* W, const void* bias, int epi,
                  void* Y, int64_t ldy, const void* res, const void* gamma, vv_ctx* ws_ctx, vv_stream st);
+int vv_rmsnorm_bf16(int M, int C, const void* x, int64_t ldx, const void* w, float eps, void* y, int64_t ldy,
+                    vv_stream st);
 /* The same with the A operand RMS-normalised on load (x * rsqrt(mean(x^2) + eps),
  * bf16, times norm_w when not NULL): the fused input_layernorm / ConvRMSNorm
  * producer of the loop's GEMMs (no bias / residual epilogues). */
@@ -117,11 +119,23 @@ int vv_gemv_tune_rw(int min_m);
  * (0 item per thread, 1 row per wave, 2 row per wave + LDS-DMA rows), dynamic
  * LDS bytes}. Replaces nothing in the reference (the plan is this engine's). */
 int vv_gemv_plan(int M, int N, int K, int xf, int has_w, int has_mod, int* out);
+/* Host-only query of the same launch decision (csrc/gemm.hip: gemm_decide) for
+ * any M and every kernel form, on a device of `cus` compute units (0: none
+ * known).  xf as above, 3 = the codec mixer prologue (M samples of one step),
+ * 4 = the attention split merge (one split); epi: the epilogue (0 store .. 6
+ * CFG + DPM step); keep: the default cache policy for the weights.
+ * out[11] = {kind (0 k_gemv1, 1 k_gemv, 2 k_gemvw, 3 FP8 GEMV, 4 k_gemm<64>,
+ * 5 k_gemm<32>, 6 k_gemm_big<1>, 7 k_gemm_big<2>, 8 k_gemm_xl, 9 rejected),
+ * 16-row A tiles, waves, K splits, weight chunks in flight, tiles per workgroup,
+ * norm prologue form, grid x, grid y, workgroup size, dynamic LDS bytes}; n is
+ * the caller's capacity in words (fails, writing nothing, when n < 11). */
+int vv_gemm_plan(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out, int n);
 /* Tuning hook (benchmarks / tests): XF-free GEMMs with >= 256 rows,
  * N % 128 == 0, K % 64 == 0 and >= 256 such tiles (or >= 2^30 MACs) take the
  * LDS-staged 128 x 128 tile (k_gemm_big, the prefill projections) with 2 LDS
- * stages (-1 / 2 = built-in) or 1 stage (1); 0 = they stay on k_gemm;
- * + 4 = any tile count (tests). */
+ * stages (2) or 1 stage (1); 0 = they stay on k_gemm; -1 / 3 = built-in: the
+ * 256 x 256 tile (k_gemm_xl) where N % 256 == 0, K % 32 == 0 and there are
+ * >= 192 such tiles, else as 2; + 4 = any tile count (tests). */
 int vv_gemm_tune_big(int mode);
 /* Diagnostic (benchmarks only): M <= 16 GEMV launches write 4 s_memrealtime
  * stamps per workgroup (start, A staged, weights streamed, epilogue stored) to
@@ -142,9 +156,6 @@ int vv_attn_prefill(int mode);
 /* Diagnostic (benchmarks only): vv_gemm_bf16 reads A in MFMA-fragment order
  * (as the packed weights; the 256 x 256 tile only). */
 int vv_gemm_tune_apack(int on);
-/* Tuning hook (benchmarks only): override the GEMV plan (waves, K splits, chunks
- * in flight, tiles per workgroup) for one weight shape N x K at M <= mmax rows;
- * up to 8 overrides; N <= 0 clears them. */
 /* Test / A-B switch: 1 (default) = at 4 < 2n <= 16 rows each head FFN layer
  * is one launch with one grid-wide hand-off (head_m16.hip; within bf16 of the
  * GEMV pair, not bitwise) while ctx is the device's only registered context;
@@ -163,17 +174,17 @@ int vv_lm_ffn_active(vv_ctx* ctx, int ntok);
 /* Diagnostic: k_lm_ffn16 launches write per-workgroup phase stamps ([256][16]
  * u64, overwritten per launch; NULL = off). */
 int vv_lm_ffn_stamps(void* buf);
-/* Diagnostic switch: the LM attention half at decode (input_layernorm .. o_proj
- * + residual, <= 16 rows, contexts <= 4,096 keys) as one launch (lm_attn.hip;
- * 1, default) or the q|k|v, attention and o_proj launches (0); whether it applies
- * to this context at ntok rows over max_pos_p1 keys; and per-workgroup phase
- * stamps of its launches ([256][16] u64, overwritten per launch; NULL = off). */
 /* Diagnostic switch: the diffusion head's step boundary (final layer + DPM of
  * step s, noisy projection of step s + 1) as one launch at 2n <= 4 rows
  * (head_fin.hip; 1, default) or the two GEMV launches (0); and whether it
  * applies to this context at n samples. */
 int vv_head_fin(int on);
 int vv_head_fin_active(vv_ctx* ctx, int n);
+/* Diagnostic switch: the LM attention half at decode (input_layernorm .. o_proj
+ * + residual, <= 16 rows, contexts <= 4,096 keys) as one launch (lm_attn.hip;
+ * 1, default) or the q|k|v, attention and o_proj launches (0); whether it applies
+ * to this context at ntok rows over max_pos_p1 keys; and per-workgroup phase
+ * stamps of its launches ([256][16] u64, overwritten per launch; NULL = off). */
 int vv_lm_attn(int on);
 int vv_lm_attn_active(vv_ctx* ctx, int ntok, int max_pos_p1);
 int vv_lm_attn_stamps(void* buf);
@@ -238,6 +249,9 @@ int vv_codec_wide_stamps(void* buf);
 /* A/B switch: 1 (default) = the balanced many-tile GEMV plan at M >= 8 (one
  * workgroup per CU, 4-5 weight tiles each); 0 = ntile / 8 workgroups. */
 int vv_gemv_tune_bal(int on);
+/* Tuning hook (benchmarks only): override the GEMV plan (waves, K splits, chunks
+ * in flight, tiles per workgroup) for one weight shape N x K at M <= mmax rows;
+ * up to 8 overrides; N <= 0 clears them. */
 int vv_gemv_tune_shape(int N, int K, int mmax, int nw, int ks, int u, int tpw);
 /* Test switch: 1 (default) = the q|k|v RoPE epilogue reads the engine's
  * per-position bf16 cos / sin table; 0 = computes cosf / sinf inline
@@ -285,8 +299,6 @@ int vv_codec_stage_active(vv_ctx* ctx);
  * records per-workgroup s_memrealtime stamps into buf ([256][64] u64;
  * nullptr: off). */
 int vv_codec_stage_stamps(void* buf, int stage);
-int vv_rmsnorm_bf16(int M, int C, const void* x, int64_t ldx, const void* w, float eps, void* y, int64_t ldy,
-                    vv_stream st);
 
 #ifdef __cplusplus
 }

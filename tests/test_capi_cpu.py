@@ -107,6 +107,90 @@ def test_gemv_plan_rules():
     assert _plan(2, 17920, 1536, NORM, w=True)["rw"] == 1
 
 
+KINDS = ("GEMV1", "GEMV", "GEMVW", "GEMV_W8", "GEMM64", "GEMM32", "GEMM_BIG1", "GEMM_BIG2", "GEMM_XL", "REJECT")
+
+
+def _gemm(M, N, K, xf=0, w=False, mod=False, epi=0, keep=0, cus=256):
+    out = (ctypes.c_int * 11)()
+    assert _lib.lib().vv_gemm_plan(M, N, K, xf, int(w), int(mod), epi, keep, cus, out, 11) == 0
+    p = dict(zip(("kind", "mrep", "waves", "ksplit", "u", "tpw", "rw", "grid_x", "grid_y", "block", "lds"), list(out)))
+    p["kind"] = KINDS[p["kind"]]
+    return p
+
+
+# test_gpu_gemm.py's test_tiled_store and test_gemm_big_tile shapes, and 16K-row prefill projections
+TILED = [(M, N, K) for M in (65, 200, 3200) for N, K in ((128, 32), (32, 128), (512, 128), (64, 256), (2048, 1536))] + [
+    (256, 2048, 1536), (257, 1536, 1536), (1000, 1536, 8960), (1000, 17920, 1536), (4100, 2048, 1536), (300, 1024, 512),
+    (640, 512, 128), (16384, 2048, 1536), (16384, 1536, 8960), (16384, 17920, 1536)]
+
+
+def test_gemm_launch_decision():
+    """The one launch decision (csrc/gemm.hip gemm_decide, read by launch_gemm)
+    where vv_gemv_plan cannot look: the CU-count-dependent balanced form, the
+    M > 16 kernels and the tiled ladder (host logic only)."""
+    L = _lib.lib()
+    NORM, EPI_CFG_DPM = 1, 6
+    assert L.vv_gemm_plan(16, 64, 64, 0, 0, 0, 0, 0, 256, (ctypes.c_int * 10)(), 10) != 0      # out[] too short
+    # balanced many-tile form: B = 8 LM gate|up, 1,120 tiles on 256 CUs = 5 tiles per workgroup, 2 waves each
+    p = _gemm(16, 17920, 1536, NORM, w=True, cus=256)
+    assert (p["kind"], p["tpw"], p["waves"], p["grid_x"], p["grid_y"]) == ("GEMV1", 5, 10, 256, 1)
+    p = _gemm(16, 17920, 1536, NORM, w=True, cus=0)
+    assert (p["kind"], p["tpw"], p["waves"], p["grid_x"]) == ("GEMV1", 8, 8, 140)
+    L.vv_gemv_tune_bal(0)
+    try:
+        p = _gemm(16, 17920, 1536, NORM, w=True, cus=256)
+        assert (p["kind"], p["tpw"], p["waves"], p["grid_x"]) == ("GEMV1", 8, 8, 140)
+    finally:
+        L.vv_gemv_tune_bal(1)
+    # 16 < M <= 64 with >= 256 tiles: k_gemvw, 4 tiles per 8-wave workgroup at >= 1,024 tiles
+    p = _gemm(32, 17920, 1536)
+    assert (p["kind"], p["mrep"], p["tpw"], p["grid_x"], p["block"]) == ("GEMVW", 2, 4, 280, 512)
+    L.vv_gemv_tune_wide(0)
+    try:
+        p = _gemm(32, 17920, 1536)
+        assert (p["kind"], p["mrep"]) == ("GEMV", 2)
+    finally:
+        L.vv_gemv_tune_wide(1)
+    # the tiled ladder, one shape per rung: 256² tile, 128² tile (2 / 1 LDS stages), 64- and 32-wide k_gemm
+    p = _gemm(16384, 2048, 1536)
+    assert (p["kind"], p["grid_x"], p["grid_y"], p["block"], p["lds"]) == ("GEMM_XL", 64 * 8, 1, 512, 128 * 1024)
+    p = _gemm(3200, 2048, 1536)          # 13 x 8 = 104 256² tiles (< 192), 25 x 16 = 400 128² tiles (>= 256)
+    assert (p["kind"], p["grid_x"], p["block"]) == ("GEMM_BIG2", 400, 256)
+    p = _gemm(200, 2048, 1536)           # < 256 rows: 4 x 32 = 128 64-wide workgroups
+    assert (p["kind"], p["grid_x"], p["grid_y"]) == ("GEMM64", 4, 32)
+    p = _gemm(200, 512, 128)             # 4 x 8 = 32 such workgroups (< 128): 32-wide tiles
+    assert (p["kind"], p["grid_x"], p["grid_y"]) == ("GEMM32", 4, 16)
+    assert _gemm(300, 1024, 512)["kind"] == "GEMM32"      # 24 128² tiles, < 2^30 MACs: stays on k_gemm
+    for mode, kinds in ((0, ("GEMM64", "GEMM64", "GEMM32")), (1, ("GEMM_BIG1", "GEMM_BIG1", "GEMM32")),
+                        (2, ("GEMM_BIG2", "GEMM_BIG2", "GEMM32")), (-1, ("GEMM_XL", "GEMM_BIG2", "GEMM32")),
+                        (5, ("GEMM_BIG1", "GEMM_BIG1", "GEMM_BIG1")), (7, ("GEMM_XL", "GEMM_XL", "GEMM_XL"))):
+        L.vv_gemm_tune_big(mode)
+        try:
+            got = tuple(_gemm(*s)["kind"] for s in ((16384, 2048, 1536), (3200, 2048, 1536), (300, 1024, 512)))
+        finally:
+            L.vv_gemm_tune_big(-1)
+        assert got == kinds, (mode, got)
+    # gemm_uses_xl (the A-row layout engine.cpp's producers write) = "the decision is GEMM_XL": mode 3 (-1) of
+    # vv_gemm_tune_big, >= 256 rows, N % 256 == 0, K % 32 == 0 and >= 192 such tiles, or any count with + 4
+    for mode in (-1, 0, 1, 2, 4, 5, 6, 7):
+        L.vv_gemm_tune_big(mode)
+        try:
+            got = [_gemm(*s)["kind"] == "GEMM_XL" for s in TILED]
+        finally:
+            L.vv_gemm_tune_big(-1)
+        big, any_count = (3, 0) if mode < 0 else (mode & 3, mode & 4)
+        want = [big == 3 and M >= 256 and N % 256 == 0 and K % 32 == 0 and (-(-M // 256) * (N // 256) >= 192 or
+                                                                           bool(any_count)) for M, N, K in TILED]
+        assert got == want, mode
+    assert any(want) and not all(want)
+    # an A transform keeps the prefill shape off the LDS-staged tiles
+    assert _gemm(16384, 2048, 1536, NORM, w=True)["kind"] == "GEMM64"
+    # no kernel: N % 32 != 0 on the tiled path, the CFG + DPM epilogue at more than 16 rows
+    assert _gemm(128, 48, 64)["kind"] == "REJECT" and _gemm(64, 48, 64)["kind"] == "GEMV"
+    assert _gemm(18, 64, 1536, NORM, epi=EPI_CFG_DPM)["kind"] == "REJECT"
+    assert _gemm(16, 64, 1536, NORM, epi=EPI_CFG_DPM)["kind"] == "GEMV1"
+
+
 def _attn(ntok, max_pos_p1, lm_slots=2):
     out = (ctypes.c_int * 6)()
     assert _lib.lib().vv_attn_pass_plan(ntok, lm_slots, 128, 2, max_pos_p1, out) == 0

@@ -33,6 +33,7 @@
 //            release / ticket / acquire, Guideline 16) only for few-tile shapes.
 //   k_gemm : M > 64 (codec stages at T >= 8, LM prefill).  64 x BN workgroup
 //            tile, 4 waves of 32 x BN/2, operands straight from L2.
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -122,7 +123,7 @@ DEV bool splitk_handoff(const GemmArgs& a, float* red, int TILE, unsigned* last_
 // (Rejected variants -- weights issued twice as deep before the prologue, a
 // one-round-trip M = 16 prologue, epilogue operands prefetched at kernel start --
 // are recorded with their measurements in DESIGN.md and no longer built.)
-// TPW = 5: the balanced many-tile form (gemv_resolve): one workgroup per CU, 4 or
+// TPW = 5: the balanced many-tile form (gemm_decide): one workgroup per CU, 4 or
 // 5 tiles each, 2 waves per tile (10 waves)
 constexpr int gemv1_max_waves(int tpw) { return tpw == 5 ? 10 : 8; }
 template <int U, int XF, bool KEEP = false, int TPW = 1, int RW = 0>
@@ -183,7 +184,7 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
   constexpr int Q = 4;   // A items per thread on the fast path
   const bool fast = a.M * n8 <= Q * NT;
   // row-per-wave norm prologue: items per lane per row (IPR) x rows per wave (RPW)
-  // (RW instantiations only; the host picks them for eligible shapes, gemv1_rw)
+  // (RW instantiations only; the host picks them for eligible shapes, gemm_decide)
   const int ipr = n8 >> 6, rpw = (a.M + NW - 1) / NW;
   const int rw = ipr == 3 && rpw == 1 ? 31 : ipr == 3 ? 32 : 71;
   // whole rows per wave: loads (A, norm weight, adaLN shift / scale; all
@@ -882,42 +883,6 @@ __global__ void __launch_bounds__(512) k_gemvw(GemmArgs a) {
   }
 }
 
-template <int MREP, int TPW>
-static void launch_gemvw_t(const GemmArgs& a, hipStream_t st) {
-  const dim3 grid((a.N / 16 + TPW - 1) / TPW);
-  if (a.keep) hipLaunchKernelGGL((k_gemvw<MREP, TPW, true>), grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((k_gemvw<MREP, TPW, false>), grid, dim3(512), 0, st, a);
-}
-
-static std::atomic<int> g_gemvw{1};   // diagnostic: 0 = k_gemv for every 16 < M <= 64 (vv_gemv_tune_wide)
-extern "C" int vv_gemv_tune_wide(int on) {
-  g_gemvw = on;
-  return 0;
-}
-
-// 16 < M <= 64, >= 256 tiles, plain A (no transform), one K split
-static bool launch_gemvw(const GemmArgs& a, hipStream_t st) {
-  const int tiles = a.N / 16;
-  if (!g_gemvw || a.M <= 16 || a.M > 64 || tiles < 256 || a.xf.kind != XF_NONE || a.epi.kind == EPI_CFG_DPM)
-    return false;
-  const int mrep = (a.M + 15) / 16;
-  const int tpw = tiles >= 1024 ? 4 : tiles >= 512 ? 2 : 1;   // ~256-340 workgroups
-  if (mrep == 2) {
-    if (tpw == 4) launch_gemvw_t<2, 4>(a, st);
-    else if (tpw == 2) launch_gemvw_t<2, 2>(a, st);
-    else launch_gemvw_t<2, 1>(a, st);
-  } else if (mrep == 3) {
-    if (tpw == 4) launch_gemvw_t<3, 4>(a, st);
-    else if (tpw == 2) launch_gemvw_t<3, 2>(a, st);
-    else launch_gemvw_t<3, 1>(a, st);
-  } else {
-    if (tpw == 4) launch_gemvw_t<4, 4>(a, st);
-    else if (tpw == 2) launch_gemvw_t<4, 2>(a, st);
-    else launch_gemvw_t<4, 1>(a, st);
-  }
-  return true;
-}
-
 // ------------------------------------------------------------------ tiled GEMM (M > 64)
 template <int BN, int XF>
 __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
@@ -1107,276 +1072,6 @@ __global__ void __launch_bounds__(256) k_gemm_big(GemmArgs a) {
     epi_tile(a, tm * GB_M + (wm * 4 + (i & 3)) * 16 + r, tn * GB_N + (wn * 4 + (i >> 2)) * 16, lane, v);
 #pragma unroll
     for (int k = 0; k < 15; ++k) acc[k >> 2][k & 3] = acc[(k + 1) >> 2][(k + 1) & 3];
-  }
-}
-
-// ------------------------------------------------------------------ host launch
-static std::atomic<int> g_tune_nw{0}, g_tune_ks{0}, g_tune_handoff{-1}, g_tune_waves{0}, g_tune_u{0}, g_tune_tpw{0};
-static std::atomic<int> g_gemv_bal{1};   // diagnostic (vv_gemv_tune_bal): 0 = ntile / 8 workgroups at M >= 8
-extern "C" int vv_gemv_tune_bal(int on) {
-  g_gemv_bal = on ? 1 : 0;
-  return 0;
-}
-static std::atomic<int> g_gemv_max_m{64};   // more rows than this: the tiled k_gemm (vv_gemv_tune_maxm)
-extern "C" int vv_gemv_tune_maxm(int m) {
-  g_gemv_max_m = m > 0 ? m : 64;
-  return 0;
-}
-static std::atomic<unsigned long long*> g_stamps{nullptr};
-static const bool g_shape_log = getenv("VV_GEMM_LOG") != nullptr;
-
-// diagnostic: GEMV launches record per-workgroup timestamps into buf (nullptr: off)
-extern "C" int vv_gemv_stamps(void* buf) {
-  g_stamps = (unsigned long long*)buf;
-  return 0;
-}
-
-extern "C" int vv_gemv_tune(int nw, int ks, int handoff, int target_waves, int u) {
-  g_tune_nw = nw;
-  g_tune_ks = ks;
-  g_tune_handoff = handoff;
-  g_tune_waves = target_waves;
-  g_tune_u = u;
-  return 0;
-}
-
-// diagnostic: force k_gemv1's tiles per workgroup (0: plan)
-extern "C" int vv_gemv_tune_tpw(int tpw) {
-  g_tune_tpw = tpw;
-  return 0;
-}
-
-struct GemmPlan { int nw, ksplit, u, tpw, grid = 0; };   // grid: workgroups when not ntile / tpw
-
-// Measured on MI355X (tools/gemv_sweep.py two-pass min, profiles/r01_gemv_sweep*.txt).
-// Cross-workgroup split-K only for few-tile, long-row shapes (the M >= 8 down
-// projections and codec fc2, and the M < 8 LM down projection, listed below):
-// a hand-off costs >= 2 us in the sc1 form and up to 30 us with fences, which
-// only those shapes win back in extra CUs.  Waves per workgroup (nw) and weight
-// chunks in flight per wave (u):
-//   * >= 1024 tiles (LM gate|up, head adaLN): 2 waves — every workgroup resident
-//     in the first round (4-wave groups left a second-round tail: 16.7 -> 14.0 us)
-//   * few tiles, long rows (LM / head down): 8 waves x 4; 128 tiles x K >= 8192
-//     (codec fc2): 4 x 8; at M >= 8 two workgroups split K (the shapes
-//     where the hand-off pays, profiles/r01_gemv_sweep_ks.txt: B = 8 LM down
-//     18.7 -> 15.5 us, head down 13.0 -> 12.3, B = 8 codec fc2 13.1 -> 12.0),
-//     and at M < 8 for < 128 tiles x K >= 8192 (LM down: 96 tiles reach only 96
-//     CUs; same-box interleaved A/B, 5 pairs: B = 1 step 3.749 -> 3.725 ms,
-//     B = 2 4.41 -> 4.30 ms)
-//   * 16 < M <= 64 (k_gemv): 4 waves, 1 for >= 1024 tiles (the batched head
-//     adaLN, M = 2 x 10 steps: 35 -> 20.5 us)
-//   * few tiles, short rows (qkv, o_proj): 4 x 8, all chunks in flight at once
-//   * 8 <= M <= 16 otherwise: 8 x 2; with many tiles the workgroup owns tpw
-//     tiles that share one staging of the A rows (tools/gemv_sweep.py --tpw,
-//     profiles/r01_gemv_sweep_tpw.txt: B = 8 LM gate|up 30.5 -> 20.0 us, head
-//     gate|up 4 tiles per group 15.6 us)
-// diagnostic (vv_gemv_tune_shape): plan overrides for one (N, K) at M <= m_max,
-// for same-box A/Bs of a single shape inside the loop (tools/ab_bench.py)
-struct ShapeTune { int N, K, mmax, nw, ks, u, tpw; };
-static ShapeTune g_shape_tune[8];
-static std::atomic<int> g_nshape_tune{0};
-extern "C" int vv_gemv_tune_shape(int N, int K, int mmax, int nw, int ks, int u, int tpw) {
-  if (N <= 0) {
-    g_nshape_tune = 0;
-    return 0;
-  }
-  const int n = g_nshape_tune;
-  if (n >= 8) return 1;
-  g_shape_tune[n] = {N, K, mmax, nw, ks, u, tpw};
-  g_nshape_tune = n + 1;   // published after the entry (seq_cst store)
-  return 0;
-}
-
-static GemmPlan gemv_plan(int N, int K, int M) {
-  const int ntune = g_nshape_tune;
-  for (int i = 0; i < ntune; ++i) {
-    const ShapeTune& s = g_shape_tune[i];
-    if (s.N == N && s.K == K && M <= s.mmax) return {s.nw, s.ks, s.u, s.tpw};
-  }
-  const int chunks = K / 32, tiles = N / 16;
-  int nw = 4, ks = 1, u = 4, tpw = 1;
-  if (tiles <= 128 && chunks >= 128) {
-    if (M >= 8) {   // batched rows: 2-way split-K (sc1 hand-off) reaches 2x the CUs
-      ks = 2;
-      if (chunks == 256 && tiles == 128) nw = 8;   // codec fc2, C = 2,048: 8 x 4 (B = 8 in-loop A/B: -53 us per step)
-      else if (chunks >= 256 && M <= 16) {
-        // long rows: split K until the workgroup's A slice fits k_gemv1's 64 KB of
-        // LDS (staged once) instead of k_gemv's per-wave A fragment reads from L2
-        // (LM down at B = 8, M 16 x K 8,960: 5 ways; B = 8 step 5.15 -> 5.05 ms in
-        // interleaved in-loop runs, profiles/r03_gemv_rw_ab.txt; the same rule for
-        // the codec fc2 above cost +20 us); 8 waves x 4 chunks
-        while (ks < 8 && (size_t)M * ((chunks + ks - 1) / ks * 32 + 8) * 2 > 65536) ++ks;
-        nw = 8;
-      } else if (chunks >= 256) u = 8;
-      else {
-        nw = 8;
-        // 4 splits at M > 16 (the codec fc2 at C = 1,024, B = 8: 64 rows x N 1,024 x
-        // K 4,096 on 64 tiles; interleaved in-loop pairs, B = 8 step 3.921 / 3.923 ->
-        // 3.893 / 3.896 ms; 8 splits x 2 chunks 3.935)
-        if (M > 16) ks = 4;
-      }
-    } else if (tiles < 128 && chunks >= 256) {   // M < 8 LM down: 2-way split-K, 8 waves x 4
-      ks = 2;
-      nw = 8;
-    } else if (tiles == 128 && chunks >= 256) {
-      if (chunks == 256) nw = 8;   // codec fc2 at C = 2,048 (K 8,192): 8 x 4 (in-loop A/Bs below)
-      else u = 8;
-    } else {
-      nw = 8;
-    }
-  } else if (M > 16) {
-    nw = tiles >= 1024 ? 1 : 4;   // k_gemv (A from L2 per chunk): batched head adaLN 35 -> 20.5 us
-  } else if (M >= 8 && tiles <= 8 && chunks >= 32) {
-    // the head's final layer (N 64, K 1,536: 4 tiles) at B = 8: 8-way split-K so 32
-    // workgroups share the 16-row RMSNorm prologue and the stream (interleaved
-    // in-loop pairs: B = 8 step -20..-40 us; at M = 2 the hand-off costs more
-    // than it saves, +20..+50 us)
-    nw = 8;
-    u = 2;
-    ks = 8;
-  } else if (M >= 8) {
-    nw = 8;
-    u = 2;
-    if (tiles >= 1024) {  // many tiles: 8 tiles per workgroup (one wave each) share one A staging
-      tpw = 8;
-      u = M > 8 ? 4 : 8;
-    } else if (tiles >= 512) {
-      // 2 tiles per workgroup (256 workgroups: the codec fc1 at C = 2,048, N 8,192 x
-      // K 2,048, B = 8) -- 4 reached only 128 CUs; interleaved in-loop pairs, B = 8
-      // step 3.953 / 3.948 -> 3.927 / 3.920 ms (tools/ab_bench.py gemv_tune_shape)
-      tpw = 2;
-      u = 4;
-    }
-  } else if (tiles >= 1024) {
-    // (VibeVoice-Large's K 3,584 rows too: 4 waves x 2 chunks won the bare-GEMV
-    // sweep, 46.1 -> 43.8 us, but lost in the loop, 7.07 -> 7.15 ms per step)
-    nw = 2;
-  } else if (tiles <= 128) {
-    // LM q|k|v (128 tiles x K 1,536) with codec fc2 above: 8 waves x 4 chunks
-    // instead of 4 x 8, interleaved in-loop pairs -5 .. -26 us per B = 1 step
-    if (tiles == 128 && chunks <= 64) nw = 8;
-    else u = 8;
-  } else if (tiles >= 512 && chunks <= 64) {
-    u = 2;   // head gate|up (576 tiles x K 1,536): 6 interleaved in-loop pairs, B = 1 step -13 us vs u = 4
-  }
-  if (g_tune_waves > 0) {
-    int wpt = (g_tune_waves + tiles - 1) / tiles;
-    const int maxw = (chunks + 3) / 4;
-    if (wpt > maxw) wpt = maxw;
-    if (wpt < 1) wpt = 1;
-    nw = wpt < 4 ? wpt : 4;
-    ks = (wpt + nw - 1) / nw;
-  }
-  if (g_tune_nw > 0) nw = g_tune_nw;
-  if (g_tune_ks > 0) ks = g_tune_ks;
-  if (g_tune_u > 0) u = g_tune_u;
-  if (g_tune_tpw > 0) tpw = g_tune_tpw;
-  if (ks > chunks) ks = chunks;
-  return {nw, ks, u, tpw};
-}
-
-static int max_waves(int) { return 8; }
-
-// k_gemv1's dynamic LDS: the staged A slice (+ per-item sums of squares for
-// the fused RMSNorm).  Built-in limit 64 KB.  Up to GEMV1_LDS_MAX is possible
-// with the per-kernel opt-in (one workgroup may hold 160 KiB; k_gemv1's static
-// arrays take ~8.3 KB) so the B = 8 down projections (M = 16 rows of 4,480 /
-// 2,304 columns per K split) stage A once per workgroup instead of k_gemv's
-// per-wave fragment loads -- measured slower (B = 8 step 5.51 -> 5.83 ms: one
-// workgroup per CU leaves too few weight loads in flight), so it stays a hook.
-constexpr size_t GEMV1_LDS_MAX = 151552, GEMV1_LDS_DEFAULT = 65536;
-static std::atomic<size_t> g_gemv1_lds_max{GEMV1_LDS_DEFAULT};   // diagnostic (vv_gemv_tune_lds)
-extern "C" int vv_gemv_tune_lds(int bytes) {
-  g_gemv1_lds_max = bytes > 0 && (size_t)bytes <= GEMV1_LDS_MAX ? (size_t)bytes : GEMV1_LDS_DEFAULT;
-  return 0;
-}
-static size_t gemv1_lds(const GemmArgs& a) {
-  const int nchunk = a.K >> 5;
-  const size_t kw = ((nchunk + a.ksplit - 1) / a.ksplit) * 32;
-  const size_t xs = ((size_t)a.M * (kw + 8) * sizeof(bf16) + 15) & ~(size_t)15;
-  return xs + (a.xf.kind == XF_NORM ? (size_t)a.M * (kw / 8) * sizeof(float) : 0);
-}
-static bool gemv1_fits(const GemmArgs& a) { return gemv1_lds(a) <= g_gemv1_lds_max; }
-
-template <int U, int XF, bool KEEP, int TPW, int RW>
-static void go_gemv1(const GemmArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  if (lds > 65536) {   // > 64 KB of dynamic LDS needs the opt-in, once per instantiation
-    static const bool attr = hipFuncSetAttribute((const void*)k_gemv1<U, XF, KEEP, TPW, RW>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)GEMV1_LDS_MAX) == hipSuccess;
-    (void)attr;   // a refused opt-in surfaces as the launch error
-  }
-  hipLaunchKernelGGL((k_gemv1<U, XF, KEEP, TPW, RW>), grid, block, lds, st, a);
-}
-
-// Row-per-wave norm prologue (k_gemv1's RW form) for this launch?  Whole rows
-// of K = 1,536 (3 items per lane) at up to 2 rows per wave, or K = 3,584 (7
-// items) at one row per wave without adaLN operands (their registers would cost
-// occupancy).  A separate instantiation: compiled into the item-per-thread
-// kernels it cost them registers / SGPR spills (B = 1 step 3.57 -> 3.66 ms).
-// Interleaved same-box runs (profiles/r03_gemv_rw_ab.txt): B = 8 step 5.45-5.47
-// -> 5.14-5.16 ms (M = 16 LM gate|up 19.98 -> 17.11 us, q|k|v 11.20 -> 8.63,
-// head gate|up 15.62 -> 12.45 in tools/gemv_variants.py), VibeVoice-Large B = 1
-// 7.14 -> 6.85 ms (K = 3,584 rows), 1.5B B = 1 3.597 -> 3.588 ms.
-// Diagnostic: vv_gemv_tune_rw(min rows; 99 = off).
-// The K = 3,584 adaLN rows (VibeVoice-Large head) take the LDS-DMA form (RW 2).
-// Diagnostic: vv_gemv_tune_rw(min rows; 99 = off; -1 = built-in without RW 2).
-static std::atomic<int> g_rw_min_m{1};
-static std::atomic<bool> g_rw_dma{true};
-extern "C" int vv_gemv_tune_rw(int min_m) {
-  g_rw_min_m = min_m > 0 ? min_m : 1;
-  g_rw_dma = min_m >= 0;
-  return 0;
-}
-static int gemv1_rw(const GemmArgs& a, int nw) {
-  if (a.xf.kind != XF_NORM || a.ksplit != 1 || a.M < g_rw_min_m || a.K % 512) return 0;
-  const int ipr = a.K / 512, rpw = (a.M + nw - 1) / nw;
-  if (ipr == 3 && rpw <= 2) return 1;
-  if (ipr == 7 && rpw == 1) return !a.xf.mod ? 1 : g_rw_dma ? 2 : 0;
-  return 0;
-}
-
-// TPW is a template argument so the one-tile form (every M < 8 launch) keeps
-// its straight-line index math (a runtime tiles-per-group cost 1 us per launch)
-template <int XF, int TPW, int RW>
-static void launch_gemv1_rw(const GemmArgs& a, int u, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  if (a.keep) {
-    if (u == 4) go_gemv1<4, XF, true, TPW, RW>(a, grid, block, lds, st);
-    else if (u == 2) go_gemv1<2, XF, true, TPW, RW>(a, grid, block, lds, st);
-    else go_gemv1<8, XF, true, TPW, RW>(a, grid, block, lds, st);
-  } else {
-    if (u == 4) go_gemv1<4, XF, false, TPW, RW>(a, grid, block, lds, st);
-    else if (u == 2) go_gemv1<2, XF, false, TPW, RW>(a, grid, block, lds, st);
-    else go_gemv1<8, XF, false, TPW, RW>(a, grid, block, lds, st);
-  }
-}
-template <int XF, int TPW>
-static void launch_gemv1(const GemmArgs& a, int u, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  const int rw = XF == XF_NORM ? gemv1_rw(a, block.x / 64) : 0;
-  if (rw == 1) launch_gemv1_rw<XF_NORM, TPW, 1>(a, u, grid, block, lds, st);
-  else if (rw == 2 && TPW == 1) launch_gemv1_rw<XF_NORM, 1, 2>(a, u, grid, block, lds, st);
-  else launch_gemv1_rw<XF, TPW, 0>(a, u, grid, block, lds, st);
-}
-
-template <int XF>
-static void launch_gemv_xf(const GemmArgs& a, int mrep, int u, dim3 grid, dim3 block, hipStream_t st) {
-  if (mrep == 1 && !gemv1_fits(a)) {
-    hipLaunchKernelGGL((k_gemv<1, 8, XF>), grid, block, 0, st, a);
-    return;
-  }
-  if (mrep == 1) {
-    const size_t lds = gemv1_lds(a);
-    if (a.tpw == 1) launch_gemv1<XF, 1>(a, u, grid, block, lds, st);
-    else if (a.tpw == 2) launch_gemv1<XF, 2>(a, u, grid, block, lds, st);
-    else if (a.tpw == 4) launch_gemv1<XF, 4>(a, u, grid, block, lds, st);
-    else if (a.tpw == 5) launch_gemv1<XF, 5>(a, u, grid, block, lds, st);
-    else launch_gemv1<XF, 8>(a, u, grid, block, lds, st);
-    return;
-  }
-  switch (mrep) {
-    case 2: hipLaunchKernelGGL((k_gemv<2, 4, XF>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_gemv<3, 2, XF>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_gemv<4, 2, XF>), grid, block, 0, st, a); break;
   }
 }
 
@@ -1653,61 +1348,198 @@ __global__ void __launch_bounds__(512) k_gemm_xl(GemmArgs a) {
   }
 }
 
-// diagnostic (vv_gemm_tune_big): 0 keeps every M > 64 GEMM on k_gemm; 1 / 2 LDS
-// stages of the 128² tile (k_gemm_big); 3 (built-in) = the 256² tile (k_gemm_xl)
-// where it applies, else k_gemm_big<2>; + 4 ignores the tile-count thresholds
-static std::atomic<int> g_gemm_big{3}, g_gemm_big_any{0};
+// ------------------------------------------------------------------ host launch
+// Diagnostic state (process-wide; include/vibevoice_hip_diag.h documents each
+// setter).  g_tune holds the words, gemm_decide reads one GemmTune snapshot.
+constexpr size_t GEMV1_LDS_MAX = 151552, GEMV1_LDS_DEFAULT = 65536;   // k_gemv1's dynamic LDS (gemv1_lds below)
+struct ShapeTune { int N, K, mmax, nw, ks, u, tpw; };
+template <class I>
+struct GemmTuneT {
+  I nw{0}, ks{0}, handoff{-1}, waves{0}, u{0}, tpw{0};   // vv_gemv_tune / _tpw: 0 (-1) = the plan's
+  I bal{1};                       // vv_gemv_tune_bal: 0 = ntile / 8 workgroups at M >= 8
+  I max_m{64};                    // vv_gemv_tune_maxm: more rows than this take the tiled k_gemm
+  I wide{1};                      // vv_gemv_tune_wide: 0 = k_gemv for every 16 < M <= 64
+  I lds_max{GEMV1_LDS_DEFAULT};   // vv_gemv_tune_lds
+  I rw_min_m{1}, rw_dma{1};       // vv_gemv_tune_rw
+  // vv_gemm_tune_big: 0 keeps every M > 64 GEMM on k_gemm; 1 / 2 LDS stages of the
+  // 128² tile (k_gemm_big); 3 (built-in) = the 256² tile (k_gemm_xl) where it
+  // applies, else k_gemm_big<2>; + 4 (big_any) ignores the tile-count thresholds
+  I big{3}, big_any{0};
+  // vv_gemv_tune_shape: plan overrides for one (N, K) at M <= m_max, for same-box
+  // A/Bs of a single shape inside the loop (tools/ab_bench.py)
+  I nshape{0};
+  ShapeTune shape[8];
+};
+using GemmTune = GemmTuneT<int>;
+static GemmTuneT<std::atomic<int>> g_tune;
+static GemmTune tune_snapshot() {
+  const auto& g = g_tune;
+  GemmTune t{g.nw, g.ks, g.handoff, g.waves, g.u, g.tpw, g.bal, g.max_m, g.wide, g.lds_max, g.rw_min_m, g.rw_dma,
+             g.big, g.big_any, g.nshape};
+  for (int i = 0; i < t.nshape; ++i) t.shape[i] = g.shape[i];
+  return t;
+}
+extern "C" int vv_gemv_tune(int nw, int ks, int handoff, int target_waves, int u) {
+  g_tune.nw = nw;
+  g_tune.ks = ks;
+  g_tune.handoff = handoff;
+  g_tune.waves = target_waves;
+  g_tune.u = u;
+  return 0;
+}
+extern "C" int vv_gemv_tune_tpw(int tpw) { return g_tune.tpw = tpw, 0; }
+extern "C" int vv_gemv_tune_bal(int on) { return g_tune.bal = on ? 1 : 0, 0; }
+extern "C" int vv_gemv_tune_maxm(int m) { return g_tune.max_m = m > 0 ? m : 64, 0; }
+extern "C" int vv_gemv_tune_wide(int on) { return g_tune.wide = on, 0; }
+extern "C" int vv_gemv_tune_lds(int bytes) {
+  return g_tune.lds_max = bytes > 0 && (size_t)bytes <= GEMV1_LDS_MAX ? bytes : (int)GEMV1_LDS_DEFAULT, 0;
+}
+extern "C" int vv_gemv_tune_rw(int min_m) {
+  g_tune.rw_min_m = min_m > 0 ? min_m : 1;
+  g_tune.rw_dma = min_m >= 0;
+  return 0;
+}
 extern "C" int vv_gemm_tune_big(int mode) {
-  g_gemm_big_any = mode >= 0 && (mode & 4) ? 1 : 0;
-  g_gemm_big = mode < 0 ? 3 : mode & 3;
+  g_tune.big_any = mode >= 0 && (mode & 4) ? 1 : 0;
+  g_tune.big = mode < 0 ? 3 : mode & 3;
+  return 0;
+}
+extern "C" int vv_gemv_tune_shape(int N, int K, int mmax, int nw, int ks, int u, int tpw) {
+  if (N <= 0) return g_tune.nshape = 0, 0;
+  const int n = g_tune.nshape;
+  if (n >= 8) return 1;
+  g_tune.shape[n] = {N, K, mmax, nw, ks, u, tpw};
+  g_tune.nshape = n + 1;   // published after the entry (seq_cst store)
   return 0;
 }
 
-bool gemm_uses_xl(const GemmArgs& a) {
-  const int total_xl = ((a.M + GX_M - 1) / GX_M) * (a.N / GX_N);
-  return !(a.M <= 64 && (a.M <= 16 || a.M <= g_gemv_max_m || a.epi.kind == EPI_CFG_DPM)) && a.epi.kind != EPI_CFG_DPM &&
-         g_gemm_big == 3 && a.M >= GEMM_BIG_M && a.N % GX_N == 0 && a.K % 32 == 0 &&
-         (total_xl >= GX_MIN_TILES || g_gemm_big_any);
+// diagnostic: GEMV launches record per-workgroup timestamps into buf (nullptr: off)
+static std::atomic<unsigned long long*> g_stamps{nullptr};
+extern "C" int vv_gemv_stamps(void* buf) { return g_stamps = (unsigned long long*)buf, 0; }
+static const bool g_shape_log = getenv("VV_GEMM_LOG") != nullptr;
+
+// ------------------------------------------------------------------ the launch decision (gemm_decide)
+// Measured on MI355X (tools/gemv_sweep.py two-pass min, profiles/r01_gemv_sweep*.txt).
+// Cross-workgroup split-K only for few-tile, long-row shapes (the M >= 8 down
+// projections and codec fc2, and the M < 8 LM down projection, listed below):
+// a hand-off costs >= 2 us in the sc1 form and up to 30 us with fences, which
+// only those shapes win back in extra CUs.  Waves per workgroup (nw) and weight
+// chunks in flight per wave (u):
+//   * >= 1024 tiles (LM gate|up, head adaLN): 2 waves — every workgroup resident
+//     in the first round (4-wave groups left a second-round tail: 16.7 -> 14.0 us)
+//   * few tiles, long rows (LM / head down): 8 waves x 4; 128 tiles x K >= 8192
+//     (codec fc2): 4 x 8; at M >= 8 two workgroups split K (the shapes
+//     where the hand-off pays, profiles/r01_gemv_sweep_ks.txt: B = 8 LM down
+//     18.7 -> 15.5 us, head down 13.0 -> 12.3, B = 8 codec fc2 13.1 -> 12.0),
+//     and at M < 8 for < 128 tiles x K >= 8192 (LM down: 96 tiles reach only 96
+//     CUs; same-box interleaved A/B, 5 pairs: B = 1 step 3.749 -> 3.725 ms,
+//     B = 2 4.41 -> 4.30 ms)
+//   * 16 < M <= 64 (k_gemv): 4 waves, 1 for >= 1024 tiles (the batched head
+//     adaLN, M = 2 x 10 steps: 35 -> 20.5 us)
+//   * few tiles, short rows (qkv, o_proj): 4 x 8, all chunks in flight at once
+//   * 8 <= M <= 16 otherwise: 8 x 2; with many tiles the workgroup owns tpw
+//     tiles that share one staging of the A rows (tools/gemv_sweep.py --tpw,
+//     profiles/r01_gemv_sweep_tpw.txt: B = 8 LM gate|up 30.5 -> 20.0 us, head
+//     gate|up 4 tiles per group 15.6 us)
+struct GemvPlan { int nw, ksplit, u, tpw; };
+static GemvPlan gemv_plan(int N, int K, int M, const GemmTune& t) {
+  for (int i = 0; i < t.nshape; ++i) {
+    const ShapeTune& s = t.shape[i];
+    if (s.N == N && s.K == K && M <= s.mmax) return {s.nw, s.ks, s.u, s.tpw};
+  }
+  const int chunks = K / 32, tiles = N / 16;
+  int nw = 4, ks = 1, u = 4, tpw = 1;
+  if (tiles <= 128 && chunks >= 128) {
+    if (M >= 8) {   // batched rows: 2-way split-K (sc1 hand-off) reaches 2x the CUs
+      ks = 2;
+      if (chunks == 256 && tiles == 128) nw = 8;   // codec fc2, C = 2,048: 8 x 4 (B = 8 in-loop A/B: -53 us per step)
+      else if (chunks >= 256 && M <= 16) {
+        // long rows: split K until the workgroup's A slice fits k_gemv1's 64 KB of
+        // LDS (staged once) instead of k_gemv's per-wave A fragment reads from L2
+        // (LM down at B = 8, M 16 x K 8,960: 5 ways; B = 8 step 5.15 -> 5.05 ms in
+        // interleaved in-loop runs, profiles/r03_gemv_rw_ab.txt; the same rule for
+        // the codec fc2 above cost +20 us); 8 waves x 4 chunks
+        while (ks < 8 && (size_t)M * ((chunks + ks - 1) / ks * 32 + 8) * 2 > 65536) ++ks;
+        nw = 8;
+      } else if (chunks >= 256) u = 8;
+      else {
+        nw = 8;
+        // 4 splits at M > 16 (the codec fc2 at C = 1,024, B = 8: 64 rows x N 1,024 x
+        // K 4,096 on 64 tiles; interleaved in-loop pairs, B = 8 step 3.921 / 3.923 ->
+        // 3.893 / 3.896 ms; 8 splits x 2 chunks 3.935)
+        if (M > 16) ks = 4;
+      }
+    } else if (tiles < 128 && chunks >= 256) {   // M < 8 LM down: 2-way split-K, 8 waves x 4
+      ks = 2;
+      nw = 8;
+    } else if (tiles == 128 && chunks >= 256) {
+      if (chunks == 256) nw = 8;   // codec fc2 at C = 2,048 (K 8,192): 8 x 4 (in-loop A/Bs below)
+      else u = 8;
+    } else {
+      nw = 8;
+    }
+  } else if (M > 16) {
+    nw = tiles >= 1024 ? 1 : 4;   // k_gemv (A from L2 per chunk): batched head adaLN 35 -> 20.5 us
+  } else if (M >= 8 && tiles <= 8 && chunks >= 32) {
+    // the head's final layer (N 64, K 1,536: 4 tiles) at B = 8: 8-way split-K so 32
+    // workgroups share the 16-row RMSNorm prologue and the stream (interleaved
+    // in-loop pairs: B = 8 step -20..-40 us; at M = 2 the hand-off costs more
+    // than it saves, +20..+50 us)
+    nw = 8;
+    u = 2;
+    ks = 8;
+  } else if (M >= 8) {
+    nw = 8;
+    u = 2;
+    if (tiles >= 1024) {  // many tiles: 8 tiles per workgroup (one wave each) share one A staging
+      tpw = 8;
+      u = M > 8 ? 4 : 8;
+    } else if (tiles >= 512) {
+      // 2 tiles per workgroup (256 workgroups: the codec fc1 at C = 2,048, N 8,192 x
+      // K 2,048, B = 8) -- 4 reached only 128 CUs; interleaved in-loop pairs, B = 8
+      // step 3.953 / 3.948 -> 3.927 / 3.920 ms (tools/ab_bench.py gemv_tune_shape)
+      tpw = 2;
+      u = 4;
+    }
+  } else if (tiles >= 1024) {
+    // (VibeVoice-Large's K 3,584 rows too: 4 waves x 2 chunks won the bare-GEMV
+    // sweep, 46.1 -> 43.8 us, but lost in the loop, 7.07 -> 7.15 ms per step)
+    nw = 2;
+  } else if (tiles <= 128) {
+    // LM q|k|v (128 tiles x K 1,536) with codec fc2 above: 8 waves x 4 chunks
+    // instead of 4 x 8, interleaved in-loop pairs -5 .. -26 us per B = 1 step
+    if (tiles == 128 && chunks <= 64) nw = 8;
+    else u = 8;
+  } else if (tiles >= 512 && chunks <= 64) {
+    u = 2;   // head gate|up (576 tiles x K 1,536): 6 interleaved in-loop pairs, B = 1 step -13 us vs u = 4
+  }
+  if (t.waves > 0) {
+    int wpt = (t.waves + tiles - 1) / tiles;
+    const int maxw = (chunks + 3) / 4;
+    if (wpt > maxw) wpt = maxw;
+    if (wpt < 1) wpt = 1;
+    nw = wpt < 4 ? wpt : 4;
+    ks = (wpt + nw - 1) / nw;
+  }
+  if (t.nw > 0) nw = t.nw;
+  if (t.ks > 0) ks = t.ks;
+  if (t.u > 0) u = t.u;
+  if (t.tpw > 0) tpw = t.tpw;
+  if (ks > chunks) ks = chunks;
+  return {nw, ks, u, tpw};
 }
 
-constexpr int GEMM_BN32 = 128;   // fewer 64-wide-tile workgroups than this: 32-wide tiles
-template <int XF>
-static int launch_gemm_xf(const GemmArgs& a, hipStream_t st) {
-  // k_gemm_big only with >= one 128 x 128 tile per CU or >= 2^30 MACs: the
-  // decode loop's codec GEMMs (B = 8: 320 - 1,600 rows x 256 - 1,024 columns
-  // x K <= 1,024: 24 - 104 such tiles) are faster as k_gemm's 4x more 64 x 64
-  // workgroups (B = 8 step 5.53 ms vs 5.83), a 1K-token prompt's o / down /
-  // q|k|v projections (108 - 144 tiles, K >= 1,536) on k_gemm_big (14.5 -> 13.4 ms)
-  // k_gemm_xl with >= GX_MIN_TILES 256 x 256 tiles (16K-token prefill: 384 - 4,480 tiles)
-  const int total_xl = ((a.M + GX_M - 1) / GX_M) * (a.N / GX_N);
-  if (XF == XF_NONE && g_gemm_big == 3 && a.M >= GEMM_BIG_M && a.N % GX_N == 0 && a.K % 32 == 0 &&
-      (total_xl >= GX_MIN_TILES || g_gemm_big_any)) {
-    static const bool attr = hipFuncSetAttribute((const void*)k_gemm_xl, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)GX_LDS) == hipSuccess;   // once (thread-safe static init)
-    if (!attr) return 2;
-    hipLaunchKernelGGL(k_gemm_xl, dim3(total_xl), dim3(512), GX_LDS, st, a);
-    return 0;
-  }
-  const int total = ((a.M + GB_M - 1) / GB_M) * (a.N / GB_N);
-  if (XF == XF_NONE && g_gemm_big && a.M >= GEMM_BIG_M && a.N % GB_N == 0 && a.K % GB_K == 0 &&
-      (total >= GEMM_BIG_TILES || (long long)a.M * a.N * a.K >= (1LL << 30) || g_gemm_big_any)) {
-    if (g_gemm_big == 1) hipLaunchKernelGGL(k_gemm_big<1>, dim3(((total + 7) >> 3) * 8), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_gemm_big<2>, dim3(((total + 7) >> 3) * 8), dim3(256), 0, st, a);
-    return 0;
-  }
-  // 64-wide tiles unless that leaves fewer than GEMM_BN32 workgroups (the
-  // codec's 200-row stage: fc2 N = 256 is 16 workgroups of K = 1,024)
-  const int wg64 = ((a.M + 63) / 64) * (a.N / 64);
-  if (a.N % 64 == 0 && wg64 >= GEMM_BN32) {
-    dim3 grid((a.M + 63) / 64, a.N / 64);
-    hipLaunchKernelGGL((k_gemm<64, XF>), grid, dim3(256), 0, st, a);
-  } else if (a.N % 32 == 0) {
-    dim3 grid((a.M + 63) / 64, a.N / 32);
-    hipLaunchKernelGGL((k_gemm<32, XF>), grid, dim3(256), 0, st, a);
-  } else {
-    return 1;
-  }
-  return 0;
+// k_gemv1's dynamic LDS: the staged A slice (+ per-item sums of squares for
+// the fused RMSNorm).  Built-in limit 64 KB.  Up to GEMV1_LDS_MAX is possible
+// with the per-kernel opt-in (one workgroup may hold 160 KiB; k_gemv1's static
+// arrays take ~8.3 KB) so the B = 8 down projections (M = 16 rows of 4,480 /
+// 2,304 columns per K split) stage A once per workgroup instead of k_gemv's
+// per-wave fragment loads -- measured slower (B = 8 step 5.51 -> 5.83 ms: one
+// workgroup per CU leaves too few weight loads in flight), so it stays a hook.
+static size_t gemv1_lds(int M, int K, int ksplit, bool norm) {
+  const size_t kw = ((K / 32 + ksplit - 1) / ksplit) * 32;
+  const size_t xs = ((size_t)M * (kw + 8) * sizeof(bf16) + 15) & ~(size_t)15;
+  return xs + (norm ? (size_t)M * (kw / 8) * sizeof(float) : 0);
 }
 
 // LDS of the XF_MIX GEMV (A rows + history/new rows + partial sums), 0 when
@@ -1721,8 +1553,180 @@ size_t gemv_mix_lds(int M, int T, int C) {
   return lds <= 98304 ? lds : 0;
 }
 
-// The decode-GEMV launch plan for a (M <= 64): waves, K split, tiles per
-// workgroup; sets a.ksplit / a.handoff / a.tpw (launch_gemm, vv_gemv_plan).
+// The GEMV family (M <= 64): k_gemvw, else the plan resolved against the
+// arguments -- split-to-fit, the tiles-per-workgroup gate, the balanced form --
+// and the form that runs it: k_gemv1 (special forms, RW) or k_gemv.
+static GemmLaunch gemv_decide(const GemmArgs& a, int cus, const GemmTune& t) {
+  const int tiles = a.N / 16, mrep = (a.M + 15) / 16, xk = a.xf.kind;
+  GemmLaunch d;
+  d.mrep = mrep;
+  d.keep = a.keep != 0;
+  d.handoff = t.handoff >= 0 ? t.handoff : 1;
+  // k_gemvw: 16 < M <= 64, >= 256 tiles, plain A (no transform), one K split
+  if (t.wide && a.M > 16 && tiles >= 256 && xk == XF_NONE && a.epi.kind != EPI_CFG_DPM) {
+    d.kind = GemmKind::GEMVW;
+    d.tpw = tiles >= 1024 ? 4 : tiles >= 512 ? 2 : 1;   // ~256-340 workgroups
+    d.grid_x = (tiles + d.tpw - 1) / d.tpw;
+    d.block = 512;
+    return d;
+  }
+  GemvPlan p = gemv_plan(a.N, a.K, a.M, t);
+  if (p.nw > 8) p.nw = 8;   // no plan asks for more waves (the balanced form below sets its own 10)
+  const bool can_split = a.ws && a.counters && tiles <= 65536, norm = xk == XF_NORM;
+  auto fits = [&](int ks) { return gemv1_lds(a.M, a.K, ks, norm) <= (size_t)t.lds_max; };
+  int ks = p.ksplit > 1 && !can_split ? 1 : p.ksplit;
+  // Rows too long for one workgroup to stage in k_gemv1's LDS at one K split
+  // (VibeVoice-Large's LM down projection, M = 2 x K 18,944 = 76 KB): split K
+  // until the slice fits, 8 waves x 4 chunks (tools/gemv_sweep.py --large: 48.4 ->
+  // 27.1 us), instead of k_gemv re-loading A fragments from L2 per chunk.
+  if (mrep == 1 && a.M < 8 && xk == XF_NONE && !t.ks && can_split && !fits(ks)) {
+    int s = ks;
+    while (!fits(s) && s < 4) s *= 2;
+    if (fits(s)) {
+      ks = s;
+      if (!t.nw) p.nw = 8;
+      if (!t.u) p.u = 4;
+    }
+  }
+  int nw = p.nw, tpw = 1;
+  if (mrep == 1 && ks == 1 && xk != XF_MIX && (p.tpw == 2 || p.tpw == 4 || p.tpw == 8) && nw % p.tpw == 0 && fits(1))
+    tpw = p.tpw;
+  // Many tiles at M >= 8 (B = 8 LM gate|up: 1,120 tiles): ntile / 8 = 140
+  // workgroups streamed from 140 of the 256 CUs (tools/gemv_stamps.py: 8.2 us of
+  // stream per workgroup).  Balanced form: one workgroup per CU, an even share of
+  // 4 or 5 tiles each, 2 waves per tile (k_gemv1<.., 5, ..>).
+  const bool bal = t.bal && tpw == 8 && a.M >= 8 && xk != XF_ATTN_MERGE && cus > 0 && (tiles + cus - 1) / cus == 5;
+  if (bal) {
+    tpw = 5;
+    nw = 10;
+  }
+  d.u = p.u;
+  if (xk == XF_MIX) {
+    d.lds = gemv_mix_lds(a.M, a.xf.T, a.K);
+    if (mrep != 1 || ks != 1 || !d.lds || (64 * nw) % (a.K / 8) || a.xf.ctx != 6 || a.a.idx) return GemmLaunch{};
+    // tiles per workgroup (diagnostic plans only so far): the Block1D front half is
+    // recomputed once per workgroup, so fewer, wider workgroups recompute it less
+    tpw = (p.tpw == 2 || p.tpw == 4) && nw % p.tpw == 0 ? p.tpw : 1;
+    d.u = 4;
+    d.keep = 0;
+    d.lds_optin = true;   // up to 96 KB (one workgroup may hold 160 KiB)
+  } else if (xk == XF_ATTN_MERGE) {   // o_proj on the attention's split partials: one plan form
+    if (mrep != 1 || a.xf.nsplit < 1 || a.xf.nsplit > 8 || a.K % 128 || !a.xf.part_o || !a.xf.part_ml || !a.xf.qpos)
+      return GemmLaunch{};
+    ks = tpw = 1;
+    d.u = 8;
+    d.keep = 0;
+    d.lds = gemv1_lds(a.M, a.K, 1, false);
+  } else if (mrep == 1 && fits(ks)) {
+    d.lds = gemv1_lds(a.M, a.K, ks, norm);
+    d.lds_optin = d.lds > 65536;
+    // Row-per-wave norm prologue (k_gemv1's RW form) for this launch?  Whole rows
+    // of K = 1,536 (3 items per lane) at up to 2 rows per wave, or K = 3,584 (7
+    // items) at one row per wave without adaLN operands (their registers would cost
+    // occupancy).  A separate instantiation: compiled into the item-per-thread
+    // kernels it cost them registers / SGPR spills (B = 1 step 3.57 -> 3.66 ms).
+    // Interleaved same-box runs (profiles/r03_gemv_rw_ab.txt): B = 8 step 5.45-5.47
+    // -> 5.14-5.16 ms (M = 16 LM gate|up 19.98 -> 17.11 us, q|k|v 11.20 -> 8.63,
+    // head gate|up 15.62 -> 12.45 in tools/gemv_variants.py), VibeVoice-Large B = 1
+    // 7.14 -> 6.85 ms (K = 3,584 rows), 1.5B B = 1 3.597 -> 3.588 ms.
+    // The K = 3,584 adaLN rows (VibeVoice-Large head) take the LDS-DMA form (RW 2),
+    // built at one tile per workgroup only.
+    // Diagnostic: vv_gemv_tune_rw(min rows; 99 = off; -1 = built-in without RW 2).
+    if (norm && ks == 1 && a.M >= t.rw_min_m && a.K % 512 == 0) {
+      const int ipr = a.K / 512, rpw = (a.M + nw - 1) / nw;
+      if (ipr == 3 && rpw <= 2) d.rw = 1;
+      else if (ipr == 7 && rpw == 1) d.rw = !a.xf.mod ? 1 : t.rw_dma && tpw == 1 ? 2 : 0;
+    }
+  }
+  // k_gemv1 (d.lds set), else k_gemv: mrep > 1, or the A slice does not fit
+  d.kind = d.lds ? GemmKind::GEMV1 : GemmKind::GEMV;
+  d.xf = xk;
+  d.ksplit = ks;
+  d.tpw = tpw;
+  d.grid_x = bal ? cus : (tiles + tpw - 1) / tpw;
+  d.grid_y = ks;
+  d.block = 64 * nw;
+  return d;
+}
+
+// The tiled kernels (M > 64, or above vv_gemv_tune_maxm's rows)
+constexpr int GEMM_BN32 = 128;   // fewer 64-wide-tile workgroups than this: 32-wide tiles
+static GemmLaunch gemm_tiled_decide(const GemmArgs& a, const GemmTune& t) {
+  GemmLaunch d;
+  d.xf = a.xf.kind == XF_NORM || a.xf.kind == XF_SILU_ADD ? a.xf.kind : XF_NONE;
+  d.block = 256;
+  // k_gemm_big only with >= one 128 x 128 tile per CU or >= 2^30 MACs: the
+  // decode loop's codec GEMMs (B = 8: 320 - 1,600 rows x 256 - 1,024 columns
+  // x K <= 1,024: 24 - 104 such tiles) are faster as k_gemm's 4x more 64 x 64
+  // workgroups (B = 8 step 5.53 ms vs 5.83), a 1K-token prompt's o / down /
+  // q|k|v projections (108 - 144 tiles, K >= 1,536) on k_gemm_big (14.5 -> 13.4 ms)
+  // k_gemm_xl with >= GX_MIN_TILES 256 x 256 tiles (16K-token prefill: 384 - 4,480 tiles)
+  const bool big_rows = d.xf == XF_NONE && a.M >= GEMM_BIG_M;
+  const int total_xl = ((a.M + GX_M - 1) / GX_M) * (a.N / GX_N), total = ((a.M + GB_M - 1) / GB_M) * (a.N / GB_N);
+  // 64-wide tiles unless that leaves fewer than GEMM_BN32 workgroups (the
+  // codec's 200-row stage: fc2 N = 256 is 16 workgroups of K = 1,024)
+  const int wg64 = ((a.M + 63) / 64) * (a.N / 64);
+  if (big_rows && t.big == 3 && a.N % GX_N == 0 && a.K % 32 == 0 && (total_xl >= GX_MIN_TILES || t.big_any)) {
+    d.kind = GemmKind::GEMM_XL;
+    d.grid_x = total_xl;
+    d.block = 512;
+    d.lds = GX_LDS;
+    d.lds_optin = true;
+  } else if (big_rows && t.big && a.N % GB_N == 0 && a.K % GB_K == 0 &&
+             (total >= GEMM_BIG_TILES || (long long)a.M * a.N * a.K >= (1LL << 30) || t.big_any)) {
+    d.kind = t.big == 1 ? GemmKind::GEMM_BIG1 : GemmKind::GEMM_BIG2;
+    d.grid_x = ((total + 7) >> 3) * 8;
+  } else if (a.N % 32 == 0) {
+    const bool bn64 = a.N % 64 == 0 && wg64 >= GEMM_BN32;
+    d.kind = bn64 ? GemmKind::GEMM64 : GemmKind::GEMM32;
+    d.grid_x = (a.M + 63) / 64;
+    d.grid_y = a.N / (bn64 ? 64 : 32);
+  }
+  return d;
+}
+
+GemmLaunch gemm_decide(const GemmArgs& a, int cus) {
+  const GemmTune t = tune_snapshot();
+  GemmLaunch d;
+  if (a.M <= 0 || a.K % 32 || a.N % 16 || (a.epi.kind == EPI_CFG_DPM && a.M > 16)) return d;
+  if (a.w8 && gemv_w8_serves(a)) {   // FP8 weight-only storage: its own GEMV, or dequantise and go on in bf16
+    d.kind = GemmKind::GEMV_W8;
+    return d;
+  }
+  const bool gemv = a.M <= 64 && (a.M <= 16 || a.M <= t.max_m || a.epi.kind == EPI_CFG_DPM);
+  d = gemv ? gemv_decide(a, cus, t) : gemm_tiled_decide(a, t);
+  d.dequant_w8 = a.w8 != nullptr;
+  return d;
+}
+
+bool gemm_uses_xl(const GemmArgs& a) { return gemm_decide(a, 0).kind == GemmKind::GEMM_XL; }
+
+// Host-only plan queries (no device work; tests and tools): gemm_decide's answer
+// for a shape, with placeholder operands (the decision only tests them for null).
+static GemmArgs plan_args(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep) {
+  static const bf16 dummy[8] = {};
+  static float dummy_f[1];
+  static unsigned dummy_ctr[1];
+  static const int dummy_i[1] = {};
+  GemmArgs a{};
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.epi.kind = epi;
+  a.keep = keep;
+  a.xf.kind = xf;
+  a.xf.w = has_w ? dummy : nullptr;
+  a.xf.mod = has_mod ? dummy : nullptr;
+  a.xf.T = 1;   // XF_MIX: M samples of one step
+  a.xf.ctx = 6;
+  a.xf.part_o = a.xf.part_ml = dummy_f;   // XF_ATTN_MERGE: one split
+  a.xf.qpos = dummy_i;
+  a.xf.nsplit = 1;
+  a.ws = dummy_f;
+  a.counters = dummy_ctr;
+  return a;
+}
+
 // CUs of the current device (cached per device)
 static int device_cus() {
   static std::atomic<int> cache[16];
@@ -1735,76 +1739,83 @@ static int device_cus() {
   }
   return v;
 }
-
-static GemmPlan gemv_resolve(GemmArgs& a) {
-  const int mrep = (a.M + 15) / 16;
-  GemmPlan p = gemv_plan(a.N, a.K, a.M);
-  if (p.nw > max_waves(mrep)) p.nw = max_waves(mrep);
-  a.ksplit = p.ksplit;
-  if (a.ksplit > 1 && (!a.ws || !a.counters || a.N / 16 > 65536)) a.ksplit = 1;
-  // Rows too long for one workgroup to stage in k_gemv1's LDS at one K split
-  // (VibeVoice-Large's LM down projection, M = 2 x K 18,944 = 76 KB): split K
-  // until the slice fits, 8 waves x 4 chunks (tools/gemv_sweep.py --large: 48.4 ->
-  // 27.1 us), instead of k_gemv re-loading A fragments from L2 per chunk.
-  if (mrep == 1 && a.M < 8 && a.xf.kind == XF_NONE && !g_tune_ks && a.ws && a.counters && a.N / 16 <= 65536 &&
-      !gemv1_fits(a)) {
-    GemmArgs t = a;
-    while (!gemv1_fits(t) && t.ksplit < 4) t.ksplit *= 2;
-    if (gemv1_fits(t)) {
-      a.ksplit = t.ksplit;
-      if (!g_tune_nw) p.nw = 8;
-      if (!g_tune_u) p.u = 4;
-    }
-  }
-  const int ho = g_tune_handoff;
-  a.handoff = ho >= 0 ? ho : 1;
-  a.tpw = 1;
-  if (mrep == 1 && a.ksplit == 1 && a.xf.kind != XF_MIX && (p.tpw == 2 || p.tpw == 4 || p.tpw == 8) && p.nw % p.tpw == 0 && gemv1_fits(a))
-    a.tpw = p.tpw;
-  // Many tiles at M >= 8 (B = 8 LM gate|up: 1,120 tiles): ntile / 8 = 140
-  // workgroups streamed from 140 of the 256 CUs (tools/gemv_stamps.py: 8.2 us of
-  // stream per workgroup).  Balanced form: one workgroup per CU, an even share of
-  // 4 or 5 tiles each, 2 waves per tile (k_gemv1<.., 5, ..>).
-  if (g_gemv_bal && a.tpw == 8 && a.M >= 8 && a.xf.kind != XF_ATTN_MERGE) {
-    const int ncu = device_cus(), tiles = a.N / 16;
-    if (ncu > 0 && (tiles + ncu - 1) / ncu == 5) {
-      a.tpw = 5;
-      p.nw = 10;
-      p.grid = ncu;
-    }
-  }
-  return p;
+// Any M, every kind, on a device of `cus` CUs: out[11] = {GemmKind, mrep, waves, K splits, u, tpw, rw,
+// grid x, grid y, workgroup size, dynamic LDS bytes}; n = the caller's capacity in words.
+extern "C" int vv_gemm_plan(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out,
+                            int n) {
+  if (M <= 0 || K <= 0 || K % 32 || N <= 0 || N % 16 || !out || n < 11 || xf < XF_NONE || xf > XF_ATTN_MERGE ||
+      epi < EPI_STORE || epi > EPI_CFG_DPM)
+    return 1;
+  const GemmLaunch d = gemm_decide(plan_args(M, N, K, xf, has_w, has_mod, epi, keep), cus);
+  const int o[11] = {(int)d.kind, d.mrep, (int)d.block / 64, d.ksplit, d.u, d.tpw, d.rw, (int)d.grid_x, (int)d.grid_y,
+                     (int)d.block, (int)d.lds};
+  std::copy(o, o + 11, out);
+  return 0;
+}
+// An M <= 16 GEMV on the current device: out[7] = {kernel (0 k_gemv1, 1 k_gemv: A fragments from L2), waves,
+// K splits, u, tpw, rw (0 item per thread, 1 row per wave, 2 row per wave with LDS-DMA rows), LDS bytes}.
+extern "C" int vv_gemv_plan(int M, int N, int K, int xf, int has_w, int has_mod, int* out) {
+  int o[11];
+  if (M > 16 || xf > XF_SILU_ADD || !out || vv_gemm_plan(M, N, K, xf, has_w, has_mod, EPI_STORE, 0, device_cus(), o, 11))
+    return 1;
+  const int g[7] = {o[0] != (int)GemmKind::GEMV1, o[2], o[3], o[4], o[5], o[6], o[10]};
+  std::copy(g, g + 7, out);
+  return 0;
 }
 
-// Host-only plan query (no device work; tests and tools): the kernel form and
-// launch plan launch_gemm would use for an M <= 16 GEMV.  out[7] = {kernel
-// (0 k_gemv1, 1 k_gemv: A fragments from L2), waves, K splits, chunks in flight,
-// tiles per workgroup, norm prologue form (0 item per thread, 1 row per wave,
-// 2 row per wave with LDS-DMA rows), dynamic LDS bytes}.
-extern "C" int vv_gemv_plan(int M, int N, int K, int xf, int has_w, int has_mod, int* out) {
-  if (M <= 0 || M > 16 || K % 32 || N % 16 || !out || (xf != XF_NONE && xf != XF_NORM && xf != XF_SILU_ADD)) return 1;
-  static const bf16 dummy[8] = {};
-  static unsigned dummy_ctr[1];
-  GemmArgs a{};
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.xf.kind = xf;
-  a.xf.w = has_w ? dummy : nullptr;
-  a.xf.mod = has_mod ? dummy : nullptr;
-  static float dummy_ws[1];
-  a.ws = dummy_ws;   // planning only tests these for null
-  a.counters = dummy_ctr;
-  const GemmPlan p = gemv_resolve(a);
-  const bool g1 = gemv1_fits(a);
-  out[0] = g1 ? 0 : 1;
-  out[1] = p.nw;
-  out[2] = a.ksplit;
-  out[3] = p.u;
-  out[4] = a.tpw;
-  out[5] = g1 && xf == XF_NORM ? gemv1_rw(a, p.nw) : 0;
-  out[6] = g1 ? (int)gemv1_lds(a) : 0;
-  return 0;
+// ------------------------------------------------------------------ the launcher
+// A runtime value as a template argument: f(std::integral_constant<int, V>) for
+// the V among Vs that equals v; 1 (as launch_gemm's "not served") when none does.
+template <int... Vs, class F>
+static int pick(int v, F f) {
+  int rc = 1;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+#define V(x) decltype(x)::value
+
+// The k_gemv1 builds: U x KEEP x TPW for the three plain transforms, the RW
+// forms for XF_NORM (RW 2 at one tile per workgroup), and the two special forms.
+// TPW is a template argument so the one-tile form (every M < 8 launch) keeps
+// its straight-line index math (a runtime tiles-per-group cost 1 us per launch)
+constexpr bool gemv1_built(int xf, int u, int keep, int tpw, int rw) {
+  if (xf == XF_MIX) return u == 4 && !keep && rw == 0 && (tpw == 1 || tpw == 2 || tpw == 4);
+  if (xf == XF_ATTN_MERGE) return u == 8 && !keep && rw == 0 && tpw == 1;
+  return rw == 0 || (xf == XF_NORM && (rw == 1 || tpw == 1));
+}
+static int go_gemv1(const GemmLaunch& d, const GemmArgs& a, hipStream_t st) {
+  return pick<XF_NONE, XF_NORM, XF_SILU_ADD, XF_MIX, XF_ATTN_MERGE>(d.xf, [&](auto XF) {
+    return pick<2, 4, 8>(d.u == 2 || d.u == 4 ? d.u : 8, [&](auto U) {
+      return pick<0, 1>(d.keep, [&](auto KEEP) {
+        return pick<1, 2, 4, 5, 8>(d.tpw, [&](auto TPW) {
+          return pick<0, 1, 2>(d.rw, [&](auto RW) {
+            if constexpr (gemv1_built(V(XF), V(U), V(KEEP), V(TPW), V(RW))) {
+              constexpr auto k = k_gemv1<V(U), V(XF), V(KEEP) != 0, V(TPW), V(RW)>;
+              if (d.lds_optin) {   // > 64 KB of dynamic LDS needs the opt-in, once per instantiation
+                static const bool attr = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                             V(XF) == XF_MIX ? 98304 : (int)GEMV1_LDS_MAX) == hipSuccess;
+                if (!attr) return 2;
+              }
+              hipLaunchKernelGGL(k, dim3(d.grid_x, d.grid_y), dim3(d.block), d.lds, st, a);
+              return 0;
+            } else {
+              return 1;
+            }
+          });
+        });
+      });
+    });
+  });
+}
+static int go_gemvw(const GemmLaunch& d, const GemmArgs& a, hipStream_t st) {
+  return pick<2, 3, 4>(d.mrep, [&](auto MREP) {
+    return pick<1, 2, 4>(d.tpw, [&](auto TPW) {
+      return pick<0, 1>(d.keep, [&](auto KEEP) {
+        hipLaunchKernelGGL((k_gemvw<V(MREP), V(TPW), V(KEEP) != 0>), dim3(d.grid_x), dim3(d.block), 0, st, a);
+        return 0;
+      });
+    });
+  });
 }
 
 // returns 0 ok, else an error code (see engine.cpp)
@@ -1818,8 +1829,11 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
   if (a.xf.kind == XF_NORM && a.K % 8 != 0) return 1;
   if (a.epi.kind == EPI_ROPE && (a.rope.kv.d != 128 || !a.rope.pos || !a.rope.slots)) return 1;
   if (a.epi.kind == EPI_CFG_DPM && (a.M > 16 || 2 * a.dpm.n != a.M)) return 1;
-  if (a.w8) {   // FP8 weight-only storage: its own GEMV, or dequantise this matrix and go on in bf16
-    if (gemv_w8_serves(a)) return launch_gemv_w8(a, st);
+  // (only the balanced form, M >= 8, reads the CU count: the M < 8 decode launches skip the runtime's query)
+  const GemmLaunch d = gemm_decide(a, a.M >= 8 ? device_cus() : 0);
+  if (d.kind == GemmKind::REJECT) return 1;
+  if (d.kind == GemmKind::GEMV_W8) return launch_gemv_w8(a, st);
+  if (d.dequant_w8) {
     if (!a.w8e || !a.w8_scratch || a.K % 64) return 1;
     if (int rc = launch_dequant_w8(a.w8, a.w8e, a.w8_scratch, a.N, a.K, st)) return rc;
     a.w = a.w8_scratch;
@@ -1829,56 +1843,42 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
   if (g_shape_log) {   // VV_GEMM_LOG=1: one line per launch (shape census for profiles/)
     fprintf(stderr, "vv_gemm M=%d N=%d K=%d xf=%d epi=%d\n", a.M, a.N, a.K, a.xf.kind, a.epi.kind);
   }
-  if (a.M <= 64 && (a.M <= 16 || a.M <= g_gemv_max_m || a.epi.kind == EPI_CFG_DPM)) {
-    if (launch_gemvw(a, st)) return hipGetLastError() == hipSuccess ? 0 : 2;
-    const int mrep = (a.M + 15) / 16;
-    const GemmPlan p = gemv_resolve(a);
-    dim3 grid(p.grid ? p.grid : (a.N / 16 + a.tpw - 1) / a.tpw, a.ksplit), block(64 * p.nw);
-    if (a.xf.kind == XF_MIX) {
-      const size_t lds = gemv_mix_lds(a.M, a.xf.T, a.K);
-      if (mrep != 1 || a.ksplit != 1 || !lds || (64 * p.nw) % (a.K / 8) || a.xf.ctx != 6 || a.a.idx) return 1;
-      // tiles per workgroup (diagnostic plans only so far): the Block1D front half is
-      // recomputed once per workgroup, so fewer, wider workgroups recompute it less
-      const int mt = (p.tpw == 2 || p.tpw == 4) && p.nw % p.tpw == 0 ? p.tpw : 1;
-      a.tpw = mt;
-      grid.x = (a.N / 16 + mt - 1) / mt;
-      // > 64 KB of dynamic LDS needs the opt-in (one workgroup may hold 160 KiB); once, thread-safe
-      static const bool attr =
-          hipFuncSetAttribute((const void*)k_gemv1<4, XF_MIX>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304) ==
-              hipSuccess &&
-          hipFuncSetAttribute((const void*)k_gemv1<4, XF_MIX, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              98304) == hipSuccess &&
-          hipFuncSetAttribute((const void*)k_gemv1<4, XF_MIX, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              98304) == hipSuccess;
+  a.ksplit = d.ksplit;
+  a.handoff = d.handoff;
+  a.tpw = d.tpw;
+  const dim3 grid(d.grid_x, d.grid_y), block(d.block);
+  auto xf3 = [&](auto f) { return pick<XF_NONE, XF_NORM, XF_SILU_ADD>(d.xf, f); };
+  int rc = 0;
+  switch (d.kind) {
+    case GemmKind::GEMV1: rc = go_gemv1(d, a, st); break;
+    case GemmKind::GEMVW: rc = go_gemvw(d, a, st); break;
+    case GemmKind::GEMV:   // chunks in flight per mrep: 8 / 4 / 2 / 2
+      rc = xf3([&](auto XF) {
+        if (d.mrep == 1) hipLaunchKernelGGL((k_gemv<1, 8, V(XF)>), grid, block, 0, st, a);
+        else if (d.mrep == 2) hipLaunchKernelGGL((k_gemv<2, 4, V(XF)>), grid, block, 0, st, a);
+        else if (d.mrep == 3) hipLaunchKernelGGL((k_gemv<3, 2, V(XF)>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_gemv<4, 2, V(XF)>), grid, block, 0, st, a);
+        return 0;
+      });
+      break;
+    case GemmKind::GEMM64:
+    case GemmKind::GEMM32:
+      rc = xf3([&](auto XF) {
+        if (d.kind == GemmKind::GEMM64) hipLaunchKernelGGL((k_gemm<64, V(XF)>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_gemm<32, V(XF)>), grid, block, 0, st, a);
+        return 0;
+      });
+      break;
+    case GemmKind::GEMM_BIG1: hipLaunchKernelGGL(k_gemm_big<1>, grid, block, 0, st, a); break;
+    case GemmKind::GEMM_BIG2: hipLaunchKernelGGL(k_gemm_big<2>, grid, block, 0, st, a); break;
+    default: {   // GEMM_XL
+      static const bool attr = hipFuncSetAttribute((const void*)k_gemm_xl, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)GX_LDS) == hipSuccess;   // once (thread-safe static init)
       if (!attr) return 2;
-      if (mt == 4) hipLaunchKernelGGL((k_gemv1<4, XF_MIX, false, 4>), grid, block, lds, st, a);
-      else if (mt == 2) hipLaunchKernelGGL((k_gemv1<4, XF_MIX, false, 2>), grid, block, lds, st, a);
-      else hipLaunchKernelGGL((k_gemv1<4, XF_MIX>), grid, block, lds, st, a);
-      return hipGetLastError() == hipSuccess ? 0 : 2;
+      hipLaunchKernelGGL(k_gemm_xl, grid, block, d.lds, st, a);
     }
-    if (a.xf.kind == XF_ATTN_MERGE) {   // o_proj on the attention's split partials: one plan form
-      if (mrep != 1 || a.xf.nsplit < 1 || a.xf.nsplit > 8 || a.K % 128 || !a.xf.part_o || !a.xf.part_ml || !a.xf.qpos)
-        return 1;
-      a.ksplit = 1;
-      a.tpw = 1;
-      const size_t lds = gemv1_lds(a);
-      hipLaunchKernelGGL((k_gemv1<8, XF_ATTN_MERGE, false, 1>), dim3(a.N / 16, 1), block, lds, st, a);
-      return hipGetLastError() == hipSuccess ? 0 : 2;
-    }
-    switch (a.xf.kind) {
-      case XF_NORM: launch_gemv_xf<XF_NORM>(a, mrep, p.u, grid, block, st); break;
-      case XF_SILU_ADD: launch_gemv_xf<XF_SILU_ADD>(a, mrep, p.u, grid, block, st); break;
-      default: launch_gemv_xf<XF_NONE>(a, mrep, p.u, grid, block, st); break;
-    }
-  } else {
-    if (a.epi.kind == EPI_CFG_DPM) return 1;
-    int rc;
-    switch (a.xf.kind) {
-      case XF_NORM: rc = launch_gemm_xf<XF_NORM>(a, st); break;
-      case XF_SILU_ADD: rc = launch_gemm_xf<XF_SILU_ADD>(a, st); break;
-      default: rc = launch_gemm_xf<XF_NONE>(a, st); break;
-    }
-    if (rc) return rc;
   }
+  if (rc) return rc;
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
+#undef V

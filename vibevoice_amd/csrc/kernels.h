@@ -418,6 +418,29 @@ int launch_codec_wide(const CodecWideArgs& a, int C, hipStream_t st);
 void codec_wide_oversubscribe(int on);
 
 size_t gemv_mix_lds(int M, int T, int C);
+// Which kernel a GEMM runs and with what geometry: decided once per launch by
+// gemm_decide (gemm.hip; host only, no HIP call, `cus` = the device's CUs or 0),
+// read by launch_gemm, gemm_uses_xl and the vv_gemv_plan / vv_gemm_plan queries.
+enum class GemmKind {
+  GEMV1,       // M <= 16, A slice staged in LDS (k_gemv1)
+  GEMV,        // M <= 64, A fragments from L2 (k_gemv<mrep>)
+  GEMVW,       // 16 < M <= 64, A held per K slice across several tiles (k_gemvw)
+  GEMV_W8,     // FP8 weights, M <= 16 (gemv_w8.hip owns its geometry: only the kind is set)
+  GEMM64, GEMM32, GEMM_BIG1, GEMM_BIG2, GEMM_XL,   // tiled: k_gemm<64 / 32>, k_gemm_big<1 / 2>, k_gemm_xl
+  REJECT       // no kernel serves these arguments (launch_gemm returns 1)
+};
+struct GemmLaunch {
+  GemmKind kind = GemmKind::REJECT;
+  bool dequant_w8 = false;      // FP8 weights first dequantised into w8_scratch; the rest is the bf16 decision
+  // the instantiation (u: the plan's chunks in flight; k_gemv1 is built for 2 / 4 / 8 and runs 8 for any
+  // other, k_gemv's are fixed per mrep)
+  int xf = 0, u = 0, keep = 0, tpw = 1, rw = 0, mrep = 1;
+  unsigned grid_x = 0, grid_y = 1, block = 0;
+  size_t lds = 0;               // dynamic LDS bytes
+  bool lds_optin = false;       // needs the per-kernel opt-in for > 64 KB
+  int ksplit = 1, handoff = 1;  // with tpw: what launch_gemm copies into GemmArgs for the kernels
+};
+GemmLaunch gemm_decide(const GemmArgs& a, int cus);
 int launch_gemm(GemmArgs a, hipStream_t st);
 // gemv_w8.hip: true when k_gemv_w8 runs this quantised GemmArgs (M <= 16, XF_NONE / XF_NORM
 // without adaLN, the epi_tile epilogues) and the kernel path is switched on (vv_gemv_w8)
