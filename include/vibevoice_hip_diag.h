@@ -46,16 +46,23 @@ int vv_gemm_bf16_norm(int M, int N, int K, const void* A, int64_t lda, const voi
  * [N, K] e4m3fn matrix in the byte order of weights.py:mfma_pack8
  * (csrc/gemv_w8.hip), `exps` one int8 exponent per output row (scale 2^e).
  * xf: 0 = A as is, 1 = A RMS-normalised on load (norm_w may be NULL).  epi as
- * vv_gemm_bf16 (bias, res optional).  M <= 16 rows run the FP8 GEMV, more rows
- * (or vv_gemv_w8(0)) dequantise the matrix and run the bf16 kernels. */
+ * vv_gemm_bf16 (bias, res optional).  M <= 16 rows run the FP8 GEMV; more rows
+ * run the bf16 kernel's instantiation that reads the codes itself (k_gemv,
+ * k_gemvw, k_gemm: 17 to 255 rows, and k_gemm's RMSNorm form above that); the
+ * LDS-staged prefill tiles, and every call under vv_gemv_w8(0), dequantise the
+ * matrix and run the bf16 kernels.  vv_gemm_plan_w8 answers which. */
 int vv_gemm_w8(int M, int N, int K, const void* A, int64_t lda, const void* codes, const void* exps, int xf,
                const void* norm_w, float eps, const void* bias, int epi, void* Y, int64_t ldy, const void* res,
                vv_ctx* ws_ctx, vv_stream st);
-/* Test / A-B switch: 1 (default) = quantised GEMMs of <= 16 rows run the FP8
- * GEMV (gemv_w8.hip); 0 = every quantised GEMM dequantises its matrix into the
- * scratch and runs the bf16 kernels (bit for bit a bf16 engine on the
- * dequantised weights). */
+/* Test / A-B switch: 1 (default) = quantised GEMMs read their codes in the
+ * kernel (the FP8 GEMV of gemv_w8.hip up to 16 rows, the bf16 kernels' W8
+ * instantiations above); 0 = every quantised GEMM, at every row count,
+ * dequantises its matrix into the scratch and runs the bf16 kernels (bit for
+ * bit a bf16 engine on the dequantised weights). */
 int vv_gemv_w8(int on);
+/* Process-wide count of dequantise passes (k_dequant_w8 launches) so far: it
+ * stands still while every quantised GEMM reads its codes in the kernel. */
+int vv_w8_dequant_launches(void);
 /* Test hook: after a vv_lm_forward of ntok rows on ctx (synchronises the
  * device): the q rows the last layer's q|k|v epilogue wrote ([ntok][n_heads x
  * 128], RoPE applied) and the K / V cache entries of `layer` at (slots[i],
@@ -130,6 +137,12 @@ int vv_gemv_plan(int M, int N, int K, int xf, int has_w, int has_mod, int* out);
  * norm prologue form, grid x, grid y, workgroup size, dynamic LDS bytes}; n is
  * the caller's capacity in words (fails, writing nothing, when n < 11). */
 int vv_gemm_plan(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out, int n);
+/* vv_gemm_plan for an FP8 weight-only operand (vv_gemm_w8's): out[0..10] as
+ * above for the same shape in bf16 -- the kernel that runs, on the codes or
+ * after the dequantise -- and out[11] = where the codes go: 0 the FP8 GEMV
+ * (k_gemv_w8), 1 that kernel's own W8 instantiation, 2 a dequantise pass into
+ * the scratch first.  Fails, writing nothing, when n < 12.  Host only. */
+int vv_gemm_plan_w8(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out, int n);
 /* Tuning hook (benchmarks / tests): XF-free GEMMs with >= 256 rows,
  * N % 128 == 0, K % 64 == 0 and >= 256 such tiles (or >= 2^30 MACs) take the
  * LDS-staged 128 x 128 tile (k_gemm_big, the prefill projections) with 2 LDS

@@ -125,6 +125,8 @@ EXPORTS = [
     ("vv_weights_quantized", I, [P]),
     ("vv_gemm_w8", I, [I, I, I, P, I64, P, P, I, P, F, P, I, P, I64, P, P, P]),
     ("vv_gemv_w8", I, [I]),
+    ("vv_w8_dequant_launches", I, []),
+    ("vv_gemm_plan_w8", I, [I, I, I, I, I, I, I, I, I, P, I]),
     ("vv_diag_lm_qkv", I, [P, I, I, ctypes.POINTER(I), ctypes.POINTER(I), P, P, P]),
     ("vv_diag_kv_read", I, [P, I, I, I, P, P]),
     ("vv_diag_kv_write", I, [P, I, I, I, P, P]),

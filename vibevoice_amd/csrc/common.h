@@ -52,6 +52,20 @@ DEV bf16x8 cvt8(unsigned d0, unsigned d1) {
   return __builtin_bit_cast(bf16x8, o);
 }
 
+// The same times a power of two, scale = 2^e as an f32 (w8_scale): the bf16
+// values k_dequant_w8 stores (code * 2^e[n]).  gfx950's scaled conversion does
+// both in one instruction per code pair; for e in weights.py's exponent range
+// the product is a normal f32 with 4 significant bits, so the bf16 is exact.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+DEV float w8_scale(int e) { return __uint_as_float((unsigned)(max(e, -126) + 127) << 23); }
+DEV bf16x8 cvt8s(unsigned d0, unsigned d1, float scale) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, true);
+  return (bf16x8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // V cache of one (layer, slot, kv head): positions in blocks of 32, each block
 // [128 dims][32 positions] (8 KB contiguous) -- attention's P.V operand loads
 // (8 positions of one dim per lane) then read whole 1 KB pieces instead of

@@ -708,7 +708,14 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
 
 // 16 < M <= 64: A fragments loaded straight from global / L2, transform per
 // chunk; weights ping-ponged as in k_gemv1.
-template <int MREP, int U, int XF>
+// W8 (all three tiled families below): the weight operand is GemmArgs::w8 / w8e
+// (e4m3 codes in mfma_pack8 order + one exponent per weight row, gemv_w8.hip).
+// Only the weight-fragment loads differ: a lane loads its code bytes and
+// converts them in registers to code * 2^e[n] (cvt8s) -- the bf16 values
+// k_dequant_w8 would have stored -- ahead of the same MFMA sequence: chunk order,
+// wave / K-split partition, reductions and epilogue are the bf16 instantiation's,
+// so the result is that kernel's on the dequantised matrix, bit for bit.
+template <int MREP, int U, int XF, bool W8 = false>
 __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
   __shared__ float red[8 * MREP * 256];
   __shared__ float inv_s[64];
@@ -723,6 +730,9 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
   const int c0 = b0 + part_of(b1 - b0, wave, NW);
   const int c1 = b0 + part_of(b1 - b0, wave + 1, NW);
   const bf16* wrow = a.w + (long long)(n0 >> 4) * a.K * 16 + lane * 8;  // MFMA-packed W
+  const unsigned char* wrow8 = a.w8 + (long long)(n0 >> 4) * a.K * 16 + lane * 16;   // W8: its codes
+  const float wsc = W8 ? w8_scale(a.w8e[n0 + r]) : 0.f;
+  using WF = std::conditional_t<W8, u32x2, bf16x8>;   // one chunk's weight fragment as loaded
   const bf16x8 zero8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
   if (XF == XF_NORM) {
     row_inv(a, 0, 16 * MREP, inv_s, wave, NW, lane);
@@ -743,22 +753,27 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
   for (int mr = 0; mr < MREP; ++mr) acc[mr] = (f32x4){0.f, 0.f, 0.f, 0.f};
   // each chunk's A fragments travel with its weight chunk (vmcnt waits are in
   // issue order: loading A inside compute would wait for the next batch too)
-  bf16x8 wa[U], wb[U], xa[U][MREP], xb[U][MREP];
-  auto load = [&](bf16x8 (&wf)[U], bf16x8 (&xf)[U][MREP], int c) {
+  WF wa[U], wb[U];
+  bf16x8 xa[U][MREP], xb[U][MREP];
+  // (odd_c, W8 only: the wave's range starts on an odd chunk, ldw8_chunks)
+  auto load = [&](WF (&wf)[U], bf16x8 (&xf)[U][MREP], int c, auto odd_c) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int cc = min(c + u, max(c1 - 1, 0));
 #pragma unroll
       for (int mr = 0; mr < MREP; ++mr) xf[u][mr] = *(const bf16x8*)(xrow[mr] + cc * 32);
-      wf[u] = ldw(wrow + cc * 512);
+      if constexpr (!W8) wf[u] = ldw(wrow + cc * 512);
     }
+    if constexpr (W8) ldw8_chunks<U, decltype(odd_c)::value>(wf, wrow8, c, max(c1 - 1, 0));
   };
-  auto compute = [&](bf16x8 (&wf)[U], bf16x8 (&xf)[U][MREP], int c) {
+  auto compute = [&](WF (&wf)[U], bf16x8 (&xf)[U][MREP], int c) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const bool ok = c + u < c1;
       const int cc = min(c + u, max(c1 - 1, 0));
-      const bf16x8 w = ok ? wf[u] : zero8;
+      bf16x8 w;
+      if constexpr (W8) w = ok ? cvt8s(wf[u][0], wf[u][1], wsc) : zero8;
+      else w = ok ? wf[u] : zero8;
 #pragma unroll
       for (int mr = 0; mr < MREP; ++mr) {
         bf16x8 x = (xok[mr] && ok) ? xf[u][mr] : zero8;
@@ -767,12 +782,23 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
       }
     }
   };
-  load(wa, xa, c0);
-  for (int c = c0; c < c1; c += 2 * U) {
-    load(wb, xb, c + U);
-    compute(wa, xa, c);
-    load(wa, xa, c + 2 * U);
-    compute(wb, xb, c + U);
+  auto stream = [&](auto odd_c) __attribute__((always_inline)) {
+    load(wa, xa, c0, odd_c);
+    for (int c = c0; c < c1; c += 2 * U) {
+      load(wb, xb, c + U, odd_c);
+      compute(wa, xa, c);
+      load(wa, xa, c + 2 * U, odd_c);
+      compute(wb, xb, c + U);
+    }
+  };
+  // W8: one copy of the loop per parity (wave-uniform) -- a parity test inside
+  // it would put the weight loads behind a branch -- each inlined like the one
+  // bf16 copy (out of line, the fragment arrays would live in scratch)
+  if constexpr (W8) {
+    if (c0 & 1) stream(std::true_type());
+    else stream(std::false_type());
+  } else {
+    stream(std::false_type());
   }
   const int TILE = MREP * 256;
 #pragma unroll
@@ -807,7 +833,7 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
 // before the epilogue.  A crosses L2 once per workgroup.
 constexpr int GW_NCH = 6;   // 32-column chunks per wave per K block (8 waves: 1,536 columns)
 
-template <int MREP, int TPW, bool KEEP>
+template <int MREP, int TPW, bool KEEP, bool W8 = false>
 __global__ void __launch_bounds__(512) k_gemvw(GemmArgs a) {
   __shared__ float red[8][MREP * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -824,6 +850,12 @@ __global__ void __launch_bounds__(512) k_gemvw(GemmArgs a) {
   const bf16* arow[MREP];
 #pragma unroll
   for (int mr = 0; mr < MREP; ++mr) arow[mr] = rm_bf(a.a, min(16 * mr + r, a.M - 1)) + 8 * g;
+  // W8: a wave's GW_NCH chunks of a tile are GW_NCH / 2 whole chunk pairs (its
+  // first chunk is even and K % 64 == 0), 16 bytes per lane each
+  using WB = std::conditional_t<W8, u32x4[GW_NCH / 2], bf16x8[GW_NCH]>;
+  float wsc[TPW];
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) wsc[i] = W8 ? w8_scale(a.w8e[min(t0 + i, ntile - 1) * 16 + r]) : 0.f;
   for (int kb = 0; kb < nchunk; kb += 8 * GW_NCH) {
     const int cw = kb + wave * GW_NCH;        // this wave's first chunk of the block (wave-uniform)
     if (cw >= nchunk) continue;
@@ -832,17 +864,25 @@ __global__ void __launch_bounds__(512) k_gemvw(GemmArgs a) {
     for (int c = 0; c < GW_NCH; ++c)
 #pragma unroll
       for (int mr = 0; mr < MREP; ++mr) xf[c][mr] = *(const bf16x8*)(arow[mr] + min(cw + c, nchunk - 1) * 32);
-    bf16x8 wa[GW_NCH], wb[GW_NCH];
-    auto wload = [&](bf16x8 (&w)[GW_NCH], int i) {
+    WB wa, wb;
+    auto wload = [&](WB& w, int i) {
       const int t = min(t0 + i, ntile - 1);
-      const bf16* wr = a.w + (long long)t * a.K * 16 + lane * 8;
+      if constexpr (W8) {
+        const unsigned char* wr = a.w8 + (long long)t * a.K * 16 + lane * 16;
 #pragma unroll
-      for (int c = 0; c < GW_NCH; ++c) w[c] = ldw<KEEP>(wr + min(cw + c, nchunk - 1) * 512);
+        for (int p = 0; p < GW_NCH / 2; ++p) w[p] = ldw8<KEEP>(wr + (long long)(min(cw + 2 * p, nchunk - 1) >> 1) * 1024);
+      } else {
+        const bf16* wr = a.w + (long long)t * a.K * 16 + lane * 8;
+#pragma unroll
+        for (int c = 0; c < GW_NCH; ++c) w[c] = ldw<KEEP>(wr + min(cw + c, nchunk - 1) * 512);
+      }
     };
-    auto mac = [&](bf16x8 (&w)[GW_NCH], int i) {
+    auto mac = [&](WB& w, int i) {
 #pragma unroll
       for (int c = 0; c < GW_NCH; ++c) {
-        const bf16x8 wc = cw + c < nchunk ? w[c] : zero8;   // chunks past K: zero weights
+        bf16x8 wc;   // chunks past K: zero weights
+        if constexpr (W8) wc = cw + c < nchunk ? cvt8s(w[c >> 1][2 * (c & 1)], w[c >> 1][2 * (c & 1) + 1], wsc[i]) : zero8;
+        else wc = cw + c < nchunk ? w[c] : zero8;
 #pragma unroll
         for (int mr = 0; mr < MREP; ++mr) acc[i][mr] = mfma(wc, xf[c][mr], acc[i][mr]);
       }
@@ -884,7 +924,7 @@ __global__ void __launch_bounds__(512) k_gemvw(GemmArgs a) {
 }
 
 // ------------------------------------------------------------------ tiled GEMM (M > 64)
-template <int BN, int XF>
+template <int BN, int XF, bool W8 = false>
 __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
   constexpr int NT = BN / 32;  // 16-wide n tiles per wave (wave covers BN/2 columns)
   __shared__ float inv_s[64];
@@ -899,8 +939,14 @@ __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
     __syncthreads();
   }
   const bf16* wrow[NT];
+  const unsigned char* wrow8[NT];   // W8: the codes, and each weight row's scale
+  float wsc[NT];
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) wrow[nt] = a.w + (long long)((n_base >> 4) + nt) * a.K * 16 + lane * 8;
+  for (int nt = 0; nt < NT; ++nt) {
+    wrow[nt] = a.w + (long long)((n_base >> 4) + nt) * a.K * 16 + lane * 8;
+    wrow8[nt] = a.w8 + (long long)((n_base >> 4) + nt) * a.K * 16 + lane * 16;
+    wsc[nt] = W8 ? w8_scale(a.w8e[n_base + nt * 16 + r]) : 0.f;
+  }
   // rows past M read row M - 1 (unconditional loads: a guarded load compiles to a
   // branch + a vmcnt(0) wait); their products land in rows the epilogue drops
   const bf16* xrow[2];
@@ -923,21 +969,33 @@ __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
   // two register sets of 2 chunks each: the loads of chunks c + 4 .. go out while
   // chunks c .. compute (one set in flight per round trip left the loop
   // latency-bound: the 320-row codec fc2 at C = 512, K 2,048, took 24 us)
-  bf16x8 wfA[2][NT], xfA[2][2], wfB[2][NT], xfB[2][2];
-  auto load = [&](int c, bf16x8 (&wf)[2][NT], bf16x8 (&xf)[2][2]) {
+  // W8: a set's 2 chunks are one chunk pair (c even, K % 64 == 0: never past K), 16 code bytes per lane
+  using WS = std::conditional_t<W8, u32x4[1][NT], bf16x8[2][NT]>;
+  WS wfA, wfB;
+  bf16x8 xfA[2][2], xfB[2][2];
+  auto load = [&](int c, WS& wf, bf16x8 (&xf)[2][2]) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int cc = min(c + u, nk - 1);
+      if constexpr (!W8) {
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) wf[u][nt] = *(const bf16x8*)(wrow[nt] + cc * 512);   // re-read across row tiles: default policy
+        for (int nt = 0; nt < NT; ++nt) wf[u][nt] = *(const bf16x8*)(wrow[nt] + cc * 512);   // re-read across row tiles: default policy
+      } else if (u == 0) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) wf[0][nt] = ldw8<true>(wrow8[nt] + (long long)(cc >> 1) * 1024);
+      }
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) xf[u][mt] = *(const bf16x8*)(xrow[mt] + cc * 32);
     }
   };
-  auto comp = [&](int c, bf16x8 (&wf)[2][NT], bf16x8 (&xf)[2][2]) {
+  auto comp = [&](int c, WS& wf, bf16x8 (&xf)[2][2]) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      if (c + u >= nk) {
+      bf16x8 wv[W8 ? NT : 1];   // W8: this chunk's fragments, converted once for both row tiles
+      if constexpr (W8) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) wv[nt] = cvt8s(wf[0][nt][2 * u], wf[0][nt][2 * u + 1], wsc[nt]);
+      } else if (c + u >= nk) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) wf[u][nt] = zero8;
       }
@@ -950,7 +1008,10 @@ __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma(wf[u][nt], xf[u][mt], acc[mt][nt]);
+        for (int nt = 0; nt < NT; ++nt) {
+          if constexpr (W8) acc[mt][nt] = mfma(wv[nt], xf[u][mt], acc[mt][nt]);
+          else acc[mt][nt] = mfma(wf[u][nt], xf[u][mt], acc[mt][nt]);
+        }
     }
   };
   load(0, wfA, xfA);
@@ -1695,7 +1756,18 @@ GemmLaunch gemm_decide(const GemmArgs& a, int cus) {
   }
   const bool gemv = a.M <= 64 && (a.M <= 16 || a.M <= t.max_m || a.epi.kind == EPI_CFG_DPM);
   d = gemv ? gemv_decide(a, cus, t) : gemm_tiled_decide(a, t);
-  d.dequant_w8 = a.w8 != nullptr;
+  if (a.w8) {
+    // FP8 weights above 16 rows: the chosen bf16 kernel's W8 instantiation reads the
+    // codes itself where one is built -- k_gemv<2..4>, k_gemvw and k_gemm<64 / 32>,
+    // every transform they take, K % 64 == 0 (whole chunk pairs per row).  The rest
+    // dequantises first: k_gemv1's forms gemv_w8_serves declines and k_gemv<1> (at
+    // most 16 rows), k_gemm_big / k_gemm_xl (>= 256 rows amortise one dequantise
+    // pass), and everything under vv_gemv_w8(0).
+    const bool built = (d.kind == GemmKind::GEMV && d.mrep >= 2) || d.kind == GemmKind::GEMVW ||
+                       d.kind == GemmKind::GEMM64 || d.kind == GemmKind::GEMM32;
+    d.w8_native = built && a.w8e && a.K % 64 == 0 && gemv_w8_enabled();
+    d.dequant_w8 = !d.w8_native;
+  }
   return d;
 }
 
@@ -1726,6 +1798,15 @@ static GemmArgs plan_args(int M, int N, int K, int xf, int has_w, int has_mod, i
   a.counters = dummy_ctr;
   return a;
 }
+static bool plan_bad(int M, int N, int K, int xf, int epi, const int* out) {
+  return M <= 0 || K <= 0 || K % 32 || N <= 0 || N % 16 || !out || xf < XF_NONE || xf > XF_ATTN_MERGE ||
+         epi < EPI_STORE || epi > EPI_CFG_DPM;
+}
+static void plan_words(const GemmLaunch& d, int* o) {
+  const int w[11] = {(int)d.kind, d.mrep, (int)d.block / 64, d.ksplit, d.u, d.tpw, d.rw, (int)d.grid_x, (int)d.grid_y,
+                     (int)d.block, (int)d.lds};
+  std::copy(w, w + 11, o);
+}
 
 // CUs of the current device (cached per device)
 static int device_cus() {
@@ -1743,13 +1824,23 @@ static int device_cus() {
 // grid x, grid y, workgroup size, dynamic LDS bytes}; n = the caller's capacity in words.
 extern "C" int vv_gemm_plan(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out,
                             int n) {
-  if (M <= 0 || K <= 0 || K % 32 || N <= 0 || N % 16 || !out || n < 11 || xf < XF_NONE || xf > XF_ATTN_MERGE ||
-      epi < EPI_STORE || epi > EPI_CFG_DPM)
-    return 1;
-  const GemmLaunch d = gemm_decide(plan_args(M, N, K, xf, has_w, has_mod, epi, keep), cus);
-  const int o[11] = {(int)d.kind, d.mrep, (int)d.block / 64, d.ksplit, d.u, d.tpw, d.rw, (int)d.grid_x, (int)d.grid_y,
-                     (int)d.block, (int)d.lds};
-  std::copy(o, o + 11, out);
+  if (n < 11 || plan_bad(M, N, K, xf, epi, out)) return 1;
+  plan_words(gemm_decide(plan_args(M, N, K, xf, has_w, has_mod, epi, keep), cus), out);
+  return 0;
+}
+// The same for a quantised operand (GemmArgs::w8): out[0..10] = the bf16 decision's words (what runs after a
+// dequantise, and the geometry of the W8 instantiation), out[11] = where the codes go: 0 k_gemv_w8, 1 the bf16
+// kernel's W8 instantiation, 2 dequantise into the scratch first.
+extern "C" int vv_gemm_plan_w8(int M, int N, int K, int xf, int has_w, int has_mod, int epi, int keep, int cus, int* out,
+                               int n) {
+  if (n < 12 || plan_bad(M, N, K, xf, epi, out)) return 1;
+  GemmArgs a = plan_args(M, N, K, xf, has_w, has_mod, epi, keep);
+  plan_words(gemm_decide(a, cus), out);
+  static const unsigned char dummy8[1] = {};
+  a.w8 = dummy8;
+  a.w8e = (const signed char*)dummy8;
+  const GemmLaunch q = gemm_decide(a, cus);
+  out[11] = q.kind == GemmKind::GEMV_W8 ? 0 : q.w8_native ? 1 : 2;
   return 0;
 }
 // An M <= 16 GEMV on the current device: out[7] = {kernel (0 k_gemv1, 1 k_gemv: A fragments from L2), waves,
@@ -1811,8 +1902,11 @@ static int go_gemvw(const GemmLaunch& d, const GemmArgs& a, hipStream_t st) {
   return pick<2, 3, 4>(d.mrep, [&](auto MREP) {
     return pick<1, 2, 4>(d.tpw, [&](auto TPW) {
       return pick<0, 1>(d.keep, [&](auto KEEP) {
-        hipLaunchKernelGGL((k_gemvw<V(MREP), V(TPW), V(KEEP) != 0>), dim3(d.grid_x), dim3(d.block), 0, st, a);
-        return 0;
+        return pick<0, 1>(d.w8_native, [&](auto W8) {
+          hipLaunchKernelGGL((k_gemvw<V(MREP), V(TPW), V(KEEP) != 0, V(W8) != 0>), dim3(d.grid_x), dim3(d.block), 0, st,
+                             a);
+          return 0;
+        });
       });
     });
   });
@@ -1847,25 +1941,32 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
   a.handoff = d.handoff;
   a.tpw = d.tpw;
   const dim3 grid(d.grid_x, d.grid_y), block(d.block);
-  auto xf3 = [&](auto f) { return pick<XF_NONE, XF_NORM, XF_SILU_ADD>(d.xf, f); };
+  // (XF, W8): the transform and the weight operand (W8 = d.w8_native) as template arguments
+  auto xf3 = [&](auto f) {
+    return pick<XF_NONE, XF_NORM, XF_SILU_ADD>(d.xf, [&](auto XF) {
+      return pick<0, 1>(d.w8_native, [&](auto W8) { return f(XF, std::bool_constant<V(W8) != 0>{}); });
+    });
+  };
   int rc = 0;
   switch (d.kind) {
     case GemmKind::GEMV1: rc = go_gemv1(d, a, st); break;
     case GemmKind::GEMVW: rc = go_gemvw(d, a, st); break;
     case GemmKind::GEMV:   // chunks in flight per mrep: 8 / 4 / 2 / 2
-      rc = xf3([&](auto XF) {
-        if (d.mrep == 1) hipLaunchKernelGGL((k_gemv<1, 8, V(XF)>), grid, block, 0, st, a);
-        else if (d.mrep == 2) hipLaunchKernelGGL((k_gemv<2, 4, V(XF)>), grid, block, 0, st, a);
-        else if (d.mrep == 3) hipLaunchKernelGGL((k_gemv<3, 2, V(XF)>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_gemv<4, 2, V(XF)>), grid, block, 0, st, a);
+      rc = xf3([&](auto XF, auto W8) {
+        if (d.mrep == 1) {
+          if constexpr (V(W8)) return 1;   // not built (gemm_decide)
+          else hipLaunchKernelGGL((k_gemv<1, 8, V(XF)>), grid, block, 0, st, a);
+        } else if (d.mrep == 2) hipLaunchKernelGGL((k_gemv<2, 4, V(XF), V(W8)>), grid, block, 0, st, a);
+        else if (d.mrep == 3) hipLaunchKernelGGL((k_gemv<3, 2, V(XF), V(W8)>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_gemv<4, 2, V(XF), V(W8)>), grid, block, 0, st, a);
         return 0;
       });
       break;
     case GemmKind::GEMM64:
     case GemmKind::GEMM32:
-      rc = xf3([&](auto XF) {
-        if (d.kind == GemmKind::GEMM64) hipLaunchKernelGGL((k_gemm<64, V(XF)>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_gemm<32, V(XF)>), grid, block, 0, st, a);
+      rc = xf3([&](auto XF, auto W8) {
+        if (d.kind == GemmKind::GEMM64) hipLaunchKernelGGL((k_gemm<64, V(XF), V(W8)>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_gemm<32, V(XF), V(W8)>), grid, block, 0, st, a);
         return 0;
       });
       break;

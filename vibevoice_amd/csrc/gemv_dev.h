@@ -56,6 +56,38 @@ DEV bf16x8 ldw(const bf16* p) {
   return *(const bf16x8*)p;
 }
 
+// The FP8 weight stream (codes in mfma_pack8 order, gemv_w8.hip): a lane's 16
+// bytes of a chunk pair's 1 KB block, or the 8 bytes of one chunk of it
+template <bool KEEP = false>
+DEV u32x4 ldw8(const unsigned char* p) {
+  if (!KEEP) return __builtin_nontemporal_load((const u32x4*)p);
+  return *(const u32x4*)p;
+}
+template <bool KEEP = false>
+DEV u32x2 ldw8h(const unsigned char* p) {
+  if (!KEEP) return __builtin_nontemporal_load((const u32x2*)p);
+  return *(const u32x2*)p;
+}
+// Chunks [c, c + U) of one tile's codes (wrow8: the tile's base + lane * 16),
+// one 8-byte fragment per chunk, clamped to chunk `last` as the bf16 loads are
+// (fragments past it are never multiplied).  Chunk pairs that lie whole inside
+// the batch are one 16-byte load, so a wave reads both halves of a block in one
+// instruction; only a batch that starts on an odd chunk (ODD; U is even, so
+// every batch of a wave does or none) takes its first and last chunk by halves.
+template <int U, bool ODD, bool KEEP = false>
+DEV void ldw8_chunks(u32x2 (&wf)[U], const unsigned char* wrow8, int c, int last) {
+  auto half = [&](int cc) { return ldw8h<KEEP>(wrow8 + (long long)(cc >> 1) * 1024 + (cc & 1) * 8); };
+  if (ODD) wf[0] = half(min(c, last));
+#pragma unroll
+  for (int u = ODD ? 1 : 0; u + 1 < U; u += 2) {
+    const int cc = min(c + u, last);   // even unless clamped (then neither fragment is used)
+    const u32x4 v = ldw8<KEEP>(wrow8 + (long long)(cc >> 1) * 1024);
+    wf[u] = (u32x2){v[0], v[1]};
+    wf[u + 1] = (u32x2){v[2], v[3]};
+  }
+  if (ODD) wf[U - 1] = half(min(c + U - 1, last));
+}
+
 DEV f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

@@ -28,10 +28,24 @@
 // LDS budget (M x K bf16 > 96 KB, e.g. 16 rows of K = 18,944) are staged in K
 // blocks, with a barrier between blocks.
 //
-// Everything else about a quantised GemmArgs (more than 16 rows, other
-// transforms) takes the fallback: k_dequant_w8 writes the matrix as bf16 in
+// More than 16 rows: the bf16 kernels that serve them read the codes themselves
+// (gemm.hip, their W8 instantiations; gemm_decide's w8_native) -- k_gemv<2..4>
+// and k_gemvw (17 to 64 rows), k_gemm<64 / 32> (65 to 255 rows, and any row
+// count with a transform), with every transform they are built for.  A lane
+// loads its 16 code bytes of a chunk pair (8 where a wave's K range cuts a
+// pair) and converts them in registers to code * 2^e[n] (cvt8s, common.h): the
+// bf16 values the dequantise pass would store, fed to the same MFMA sequence,
+// partition, reductions and epilogue -- bit for bit the bf16 kernel on the
+// dequantised matrix, with no dequantise pass (vv_w8_dequant_launches stands
+// still).  vv_gemm_plan_w8 answers where a shape goes.
+//
+// What is left takes the fallback: k_dequant_w8 writes the matrix as bf16 in
 // mfma_pack order into a scratch buffer and the bf16 launch runs on it -- bit
-// for bit a bf16 engine holding the dequantised weights.
+// for bit a bf16 engine holding the dequantised weights.  That is: up to 16
+// rows in a form k_gemv_w8 does not serve (adaLN operands, SiLU-add, the codec
+// mixer, the attention merge, k_gemv<1>); the LDS-staged prefill tiles
+// k_gemm_big / k_gemm_xl (>= 256 plain rows: one dequantise over hundreds of
+// rows); K % 64 != 0; and every quantised GEMM under vv_gemv_w8(0).
 #include <algorithm>
 #include <atomic>
 
@@ -44,9 +58,7 @@ constexpr int W8_U = 4;                  // chunk pairs (KB) per batch per wave;
 constexpr int W8_MAX_WAVES = 8;
 constexpr size_t W8_LDS_MAX = 98304;     // A rows staged per K block (dynamic LDS, opt-in above 64 KB)
 
-DEV u32x4 ldw8(const unsigned char* p) { return __builtin_nontemporal_load((const u32x4*)p); }
-
-// e4m3 -> bf16: cvt8 (common.h)
+// the code stream: ldw8 (gemv_dev.h); e4m3 -> bf16: cvt8 (common.h)
 
 DEV int w8_part(int len, int i, int n) { return (int)((unsigned)(len * i) / (unsigned)n); }
 
@@ -179,6 +191,9 @@ extern "C" int vv_gemv_w8(int on) {
   g_gemv_w8 = on ? 1 : 0;
   return 0;
 }
+bool gemv_w8_enabled() { return g_gemv_w8 != 0; }
+static std::atomic<unsigned> g_dequant_launches{0};   // diagnostic: k_dequant_w8 launches of this process
+extern "C" int vv_w8_dequant_launches() { return (int)(g_dequant_launches.load(std::memory_order_relaxed) & 0x7fffffffu); }
 
 bool gemv_w8_serves(const GemmArgs& a) {
   if (!g_gemv_w8 || !a.w8 || !a.w8e || a.M < 1 || a.M > 16 || a.K % 64 || a.N % 16 || a.apack || a.epi.pack) return false;
@@ -209,6 +224,7 @@ int launch_gemv_w8(const GemmArgs& a, hipStream_t st) {
 int launch_dequant_w8(const unsigned char* codes, const signed char* ex, bf16* out, int N, int K, hipStream_t st) {
   if (N % 16 || K % 64 || !codes || !ex || !out) return 1;
   const long long nitem = (long long)N * K / 16;
+  g_dequant_launches.fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL(k_dequant_w8, dim3((unsigned)((nitem + 255) / 256)), dim3(256), 0, st, codes, ex, out, K, nitem);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

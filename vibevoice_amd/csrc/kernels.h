@@ -431,7 +431,9 @@ enum class GemmKind {
 };
 struct GemmLaunch {
   GemmKind kind = GemmKind::REJECT;
-  bool dequant_w8 = false;      // FP8 weights first dequantised into w8_scratch; the rest is the bf16 decision
+  // FP8 weights above k_gemv_w8's forms: the rest is the bf16 decision, run by the kernel's W8
+  // instantiation on the codes (w8_native) or on w8_scratch after a dequantise pass (dequant_w8)
+  bool w8_native = false, dequant_w8 = false;
   // the instantiation (u: the plan's chunks in flight; k_gemv1 is built for 2 / 4 / 8 and runs 8 for any
   // other, k_gemv's are fixed per mrep)
   int xf = 0, u = 0, keep = 0, tpw = 1, rw = 0, mrep = 1;
@@ -445,6 +447,7 @@ int launch_gemm(GemmArgs a, hipStream_t st);
 // gemv_w8.hip: true when k_gemv_w8 runs this quantised GemmArgs (M <= 16, XF_NONE / XF_NORM
 // without adaLN, the epi_tile epilogues) and the kernel path is switched on (vv_gemv_w8)
 bool gemv_w8_serves(const GemmArgs& a);
+bool gemv_w8_enabled();   // vv_gemv_w8's switch: false = every quantised GEMM dequantises first
 int launch_gemv_w8(const GemmArgs& a, hipStream_t st);
 // codes [N][K] (mfma_pack8) x 2^ex[n] -> out bf16 [N][K] (mfma_pack), exact
 int launch_dequant_w8(const unsigned char* codes, const signed char* ex, bf16* out, int N, int K, hipStream_t st);
