@@ -91,8 +91,9 @@ int vv_finalize(vv_ctx* ctx);
  * either as the bf16 tensor under that name, or as the pair <name>8 (codes
  * [N, K], weights.py:mfma_pack8 order) + <name>e (int8 [N], row scale 2^e);
  * vv_finalize names the tensor when neither or half a pair is bound.  Returns 1
- * when ctx holds quantised LM weights (the one-launch LM kernels are then off),
- * else 0. */
+ * when ctx holds quantised LM weights, else 0.  (The one-launch LM attention
+ * kernel is then off; the one-launch MLP kernels run on the codes when every
+ * gu_w / down_w is bound as FP8, on bf16 when none is, and are off for a mix.) */
 int vv_weights_quantized(vv_ctx* ctx);
 /* KV cache format of the LM, per context: dtype 0 = bf16 (the default), 1 = FP8
  * (OCP e4m3): K (after RoPE) and V stored as one-byte codes in the bf16 cache's

@@ -184,6 +184,16 @@ int vv_head_m16_stamps(void* buf);
  * the one-launch block applies to this context at ntok rows. */
 int vv_lm_ffn(int on);
 int vv_lm_ffn_active(vv_ctx* ctx, int ntok);
+/* Diagnostic switch for contexts whose MLP projections (gu_w, down_w of every
+ * layer) are all bound as FP8: the one-launch block then runs in its W8 form
+ * (the same kernels reading the codes; bit for bit the bf16 form on the
+ * dequantised weights).  bits: bit 0 = at <= 2 rows (k_lm_ffn), bit 1 = at
+ * 3..16 rows (k_lm_ffn16); default 3; 0 = such a context runs the FP8 GEMV pair.
+ * Other values are an error.  vv_lm_ffn still gates both forms, a bf16 context
+ * is unaffected, and a context with some MLP projections bf16 and some FP8
+ * always runs the GEMV pair.  Bumps the workspace epoch (vv_ws_epoch), so
+ * captured graphs are re-captured. */
+int vv_lm_ffn_w8(int bits);
 /* Diagnostic: k_lm_ffn16 launches write per-workgroup phase stamps ([256][16]
  * u64, overwritten per launch; NULL = off). */
 int vv_lm_ffn_stamps(void* buf);

@@ -93,6 +93,7 @@ EXPORTS = [
     ("vv_head_m16_stamps", I, [P]),
     ("vv_lm_ffn", I, [I]),
     ("vv_lm_ffn_active", I, [P, I]),
+    ("vv_lm_ffn_w8", I, [I]),
     ("vv_lm_ffn_stamps", I, [P]),
     ("vv_head_fin", I, [I]),
     ("vv_head_fin_active", I, [P, I]),

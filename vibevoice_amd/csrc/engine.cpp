@@ -238,6 +238,10 @@ struct vv_ctx {
   // FP8 weight-only LM projections (gemv_w8.hip): bound as <name>8 (e4m3 codes,
   // mfma_pack8 order) + <name>e (int8 row exponents) instead of the bf16 <name>
   bool quantized = false;
+  // the MLP projections (gu_w, down_w of every layer), decided once at vv_finalize: the
+  // one-launch MLP kernels read one form throughout, a mixed binding keeps the GEMV pair
+  enum { MLP_BF16 = 0, MLP_W8 = 1, MLP_MIXED = 2 };
+  int mlp_form = MLP_BF16;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
   // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
   // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
@@ -1063,6 +1067,11 @@ int vv_finalize(vv_ctx* c) {
     CHK(need_lm_w(c, p + ".gu_w", 2LL * k.intermediate, H, &w.gu));
     CHK(need_lm_w(c, p + ".down_w", H, k.intermediate, &w.down));
   }
+  {
+    int n8 = 0;
+    for (const LmLayerW& w : c->lmw) n8 += (w.gu.w8 != nullptr) + (w.down.w8 != nullptr);
+    c->mlp_form = n8 == 0 ? vv_ctx::MLP_BF16 : n8 == 2 * k.n_layers ? vv_ctx::MLP_W8 : vv_ctx::MLP_MIXED;
+  }
   if (c->quantized) {
     // the fallback's scratch (launch_gemm: more than 16 rows, forms k_gemv_w8 does not
     // serve): sized once to the largest quantised matrix, never grown in a hot call
@@ -1125,7 +1134,12 @@ int vv_finalize(vv_ctx* c) {
   CHK(convnet_alloc(c->sem, 7));
   // a context that can run a grid-waiting kernel (the persistent codec stage, the
   // one-launch head layer at 16 rows, ...) counts in the device's registry (hl_register)
-  if (k.max_batch >= 2 && lm_ffn16_fits(k.hidden, k.intermediate, 16)) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
+  // (the one-launch MLP kernels in the form the MLP weights are bound in; a mixed binding runs neither)
+  const bool mlp_w8 = c->mlp_form == vv_ctx::MLP_W8, mlp_one = c->mlp_form != vv_ctx::MLP_MIXED;
+  const bool lf_fits = mlp_one && (mlp_w8 ? lm_ffn_w8_fits(k.hidden, k.intermediate, 2) : lm_ffn_fits(k.hidden, k.intermediate, 2));
+  const bool lf16_fits =
+      mlp_one && (mlp_w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, 16) : lm_ffn16_fits(k.hidden, k.intermediate, 16));
+  if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
   const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, LA_MAX_KEYS);
   const bool la_fits = lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
@@ -1140,7 +1154,7 @@ int vv_finalize(vv_ctx* c) {
   c->persist_capable = codec_stage_any(c->dec) || codec_stage_any(c->sem) || codec_wide_any(c->dec) ||
                        codec_wide_any(c->sem) ||
                        (c->head_gemv && head_m16_fits(k.hidden, k.head_ffn, 16)) ||
-                       lm_ffn_fits(k.hidden, k.intermediate, 2) || lm_ffn16_fits(k.hidden, k.intermediate, 16) || la_fits;
+                       lf_fits || lf16_fits || la_fits;
   if (c->persist_ok && !c->persist_follow && c->persist_capable && !c->hl_registered) {
     c->hl_registered = true;
     hl_register(c->device, +1);
@@ -1576,11 +1590,26 @@ extern "C" int vv_lm_ffn(int on) {   // bit 0: on; bit 1: not at 3..16 rows (k_l
   g_lm_ffn = on & 3;
   return 0;
 }
+// FP8 MLP weights: the W8 forms of the two kernels (vv_lm_ffn_w8 bit 0: at <= 2 rows, bit 1:
+// at 3..16 rows; 0 = an FP8 engine runs the k_gemv_w8 pair).  A bf16 engine does not read it.
+// Bumps the workspace epoch: graphs captured with the other path are re-captured.
+static std::atomic<int> g_lm_ffn_w8{3};
+extern "C" int vv_lm_ffn_w8(int bits) {
+  if (bits < 0 || bits > 3) FAIL("vv_lm_ffn_w8: bits 0..3 (bit 0: <= 2 rows, bit 1: 3..16 rows)");
+  g_lm_ffn_w8 = bits;
+  g_ws_epoch.fetch_add(1);
+  return 0;
+}
 static bool lm_ffn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  const bool shape = P.ntok <= 2 ? lm_ffn_fits(k.hidden, k.intermediate, P.ntok)
-                                 : (g_lm_ffn & 2) == 0 && c->lf_slab.p && lm_ffn16_fits(k.hidden, k.intermediate, P.ntok);
-  return g_lm_ffn && !c->quantized && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
+  if (c->mlp_form == vv_ctx::MLP_MIXED) return false;
+  const bool w8 = c->mlp_form == vv_ctx::MLP_W8, small = P.ntok <= 2;
+  if (w8 && !(g_lm_ffn_w8 & (small ? 1 : 2))) return false;
+  const bool shape = small ? (w8 ? lm_ffn_w8_fits(k.hidden, k.intermediate, P.ntok) : lm_ffn_fits(k.hidden, k.intermediate, P.ntok))
+                           : (g_lm_ffn & 2) == 0 && c->lf_slab.p &&
+                                 (w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, P.ntok)
+                                     : lm_ffn16_fits(k.hidden, k.intermediate, P.ntok));
+  return g_lm_ffn && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && shape && persist_on(c);
 }
 extern "C" int vv_lm_ffn_active(vv_ctx* c, int ntok) {
@@ -1606,6 +1635,10 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     a.nw = w.post_norm;
     a.gu = w.gu.w;
     a.dn = w.down.w;
+    a.gu8 = w.gu.w8;     // MLP_W8: the code forms (the launchers pick the W8 kernels)
+    a.gue = w.gu.w8e;
+    a.dn8 = w.down.w8;
+    a.dne = w.down.w8e;
     a.act = P.act;
     a.sync = (unsigned*)c->lf_sync.p;
     a.err = err_word(c);

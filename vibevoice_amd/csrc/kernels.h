@@ -287,7 +287,8 @@ struct HeadFinArgs {
 bool head_fin_fits(int H, int D, int R);
 int launch_head_fin(const HeadFinArgs& a, hipStream_t st);
 
-// ---- one LM MLP block at decode (R <= 2 rows) in one launch (lm_ffn.hip), GEMV layout weights
+// ---- one LM MLP block at decode (R <= 2 rows) in one launch (lm_ffn.hip), GEMV layout weights,
+// bf16 or FP8 (all four MLP matrices of the context in one form; a mixed binding keeps the GEMV pair)
 struct LmFfnArgs {
   const bf16* x;     // [R][ldx] hidden rows (read: the A side and the residual)
   bf16* out;         // [R][ldx] (may alias x)
@@ -302,11 +303,20 @@ struct LmFfnArgs {
   unsigned* err;     // set to 1 when the grid wait gave up
   float* slab;       // k_lm_ffn16: [48 column groups][4 hidden ranges][16][32] fp32 partials of down
   unsigned long long* stamps;   // diagnostics: [256][16] s_memrealtime per phase, or nullptr
+  // FP8 weights (the W8 forms of both kernels, run when gu8 is set; gu / dn are then unused):
+  // e4m3 codes in mfma_pack8 order + one int8 exponent per packed row (LmW::w8 / w8e), the
+  // same tiles, sums and epilogues -- bit for bit the bf16 form on the dequantised matrices
+  const unsigned char* gu8;     // gate|up codes [2F][H]
+  const signed char* gue;       // [2F]
+  const unsigned char* dn8;     // down codes [H][F]
+  const signed char* dne;       // [H]
 };
 bool lm_ffn_fits(int H, int F, int R);
+bool lm_ffn_w8_fits(int H, int F, int R);   // the W8 form's own residency
 int launch_lm_ffn(const LmFfnArgs& a, hipStream_t st);
 // the same block at 3 <= R <= 16 rows (k_lm_ffn16: down split by hidden range too, per-group tickets)
 bool lm_ffn16_fits(int H, int F, int R);
+bool lm_ffn16_w8_fits(int H, int F, int R);
 int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 
 // ---- the LM attention half at decode in one launch (lm_attn.hip): input_layernorm

@@ -22,7 +22,30 @@
 // Arithmetic: persist_dev.h hl_rows_norm (norm weight, no modulation) and
 // hl_silu_up, the residual as epi_row8's EPI_RES; the GEMM sums are fp32 MFMA sums in another
 // order than the GEMV kernels' (tests/test_gpu_lm.py: within bf16 of them).
+//
+// W8 (both kernels' second instantiation; LmFfnArgs::gu8 / gue / dn8 / dne): the
+// weights are e4m3 codes in mfma_pack8 order (gemv_w8.hip: 1 KB blocks of 16 rows
+// x 64 columns = two k-blocks, a lane's 16 bytes = its two fragments) + one int8
+// exponent per packed row.  Same tiles per workgroup, same k-blocks per wave, same
+// MFMA order per accumulator, same LDS sums and epilogues; only the weight loads
+// change: a lane streams codes (half the bytes, half the registers and LDS) and
+// converts a fragment to code * 2^e[row] (cvt8s: the bf16 value k_dequant_w8
+// stores, exactly) where the bf16 form reads it -- bit for bit the bf16 kernel on
+// the dequantised matrices (tests/test_gpu_w8_lm_ffn.py).  Every range below is
+// whole pairs but k_lm_ffn's down (35 k-blocks per wave: odd waves start on a
+// pair's second half).
+#include <type_traits>
+
 #include "persist_dev.h"
+
+// the FP8 weight stream: global and non-temporal as hl_ldnt; 16 bytes = a lane's
+// piece of a pair block, 8 bytes = one k-block's fragment of it
+typedef __attribute__((address_space(1))) const u32x4 hl_gu32x4;
+typedef __attribute__((address_space(1))) const u32x2 hl_gu32x2;
+DEV u32x4 hl_ldnt8(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x4*)p); }
+DEV u32x2 hl_ldnt8h(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x2*)p); }
+// fragment `half` (0 / 1) of a lane's 16 code bytes, scaled by the lane's row scale
+DEV bf16x8 hl_frag8(u32x4 v, int half, float sc) { return half ? cvt8s(v[2], v[3], sc) : cvt8s(v[0], v[1], sc); }
 
 namespace lf {
 constexpr int H = 1536, F = 8960, G = pk::G, RMAX = 2;
@@ -46,8 +69,18 @@ static_assert(TOTAL <= 160 * 1024 && XS_B % 16 == 0 && NW % 16 == 0 && WT % 16 =
 static_assert(RMAX * AST * 2 <= RED1_B && RED2 + 8 * 256 * 4 <= WT + WT_B, "lm ffn phase-B LDS");
 static_assert(4 * 4 + RMAX * 4 + 6 * RMAX * 8 * 2 + RMAX * 8 * 2 <= SM_B, "lm ffn small region");
 static_assert(G == pk::G, "grid waits: 256 arrivals per wait");
+// W8: pair blocks (1 KB of codes = 2 k-blocks of a tile).  The LDS regions keep
+// their offsets and hold half the bytes: gate|up tiles 4, 5 as [2][PC1] KB blocks
+// at WT; the down blocks at DN2 as [8 waves][SLOT8] slots of 512 B (this
+// workgroup's 8 rows of a pair): a wave's 17 LDS k-blocks lie in 9 pairs (+ 1
+// padding slot: a DMA moves two)
+constexpr int PC1 = KC1 / 2, PC2 = KC2 / 2, PPW1 = KPW1 / 2;   // 24 / 140 pairs per tile row; 3 per wave in gate|up
+constexpr int NPL8 = 9, SLOT8 = 10;
+static_assert(KPW1 % 2 == 0 && NLDS2 % 2 == 1 && NPL8 == (NLDS2 + 1) / 2 && SLOT8 == NPL8 + 1 &&
+              8 * SLOT8 * 512 <= RED2 - DN2 && 2 * PC1 * 1024 <= WT_B, "lm ffn W8 layout");
 }  // namespace lf
 
+template <bool W8>
 __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
   using namespace lf;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -103,8 +136,35 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
       hl_dma16<false, true>(dn_s + (wave * SLOT2 + 2 * q) * 256, dw + (long long)(wave * KPW2 + kb) * 512 + L * 8);
     }
   };
+  // W8: the same k-blocks lie in the NPL8 pair blocks from pair pl0; whole pairs
+  // (LDS DMA has no 8-byte form), this workgroup's 8 rows of each: 32 lanes x 16 B
+  // into a 512 B slot, lanes 0-31 pair 2q, 32-63 pair 2q + 1 (the 10th: padding)
+  const int pl0 = (wave * KPW2 + NREG2) >> 1;
+  auto issue_dn_lds8 = [&]() {
+    const int ln = hl_vopaque(lane);
+    const unsigned char* dw = hl_opaque(a.dn8) + (long long)(d >> 1) * PC2 * 1024;
+    const int p = ln & 31, L = 16 * (p >> 3) + 8 * (d & 1) + (p & 7);
+#pragma unroll
+    for (int q = 0; q < SLOT8 / 2; ++q) {
+      int pr = 2 * q + (ln >> 5);
+      pr = pr < NPL8 ? pr : NPL8 - 1;
+      hl_dma16<false, true>(smem + DN2 + (wave * SLOT8 + 2 * q) * 512, dw + (long long)(pl0 + pr) * 1024 + L * 16);
+    }
+  };
 
-  bf16x8 wb[NREG1 * KPW1];
+  // W8: a lane's weight registers are its 16 code bytes of a pair block (gate|up)
+  // or the 8 of one k-block (down: wq); the exponents of its row (lane & 15) of the
+  // 6 gate|up tile slots and of the down tile are loaded here, ahead of the A
+  // side, so the vmcnt immediates below count weight loads only
+  using WF = std::conditional_t<W8, u32x4, bf16x8>;
+  WF wb[W8 ? NREG1 * PPW1 : NREG1 * KPW1];
+  u32x2 wq[W8 ? NREG2 : 1];
+  int ex1[6] = {0, 0, 0, 0, 0, 0}, ex2 = 0;
+  if constexpr (W8) {   // (unconditional, clamped: no branch to wait in; read through hl_vopaque where first used)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ex1[j] = a.gue[min(t0 + j, T1 - 1) * 16 + (lane & 15)];
+    ex2 = a.dne[(owner ? d >> 1 : 0) * 16 + (lane & 15)];
+  }
   if (ctl && owner && lane < R) hl_dma16<false>(xraw_s, hl_opaque(a.x) + (long long)lane * a.ldx + col0);
   if (!ctl) {
     const int ln = hl_vopaque(lane);
@@ -117,6 +177,24 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     if (wave == 0)
 #pragma unroll
       for (int i = 0; i < NCH / 64; ++i) hl_dma16<false>(nw_s + i * 512, hl_opaque(a.nw) + (i * 64 + ln) * 8);
+    if constexpr (W8) {
+      // this wave's 6 k-blocks of a tile = 3 whole pairs: 12 register loads, 3 DMAs per LDS tile
+      const unsigned char* gw = hl_opaque(a.gu8) + (long long)t0 * PC1 * 1024 + ln * 16;
+#pragma unroll
+      for (int j = 0; j < NREG1; ++j)
+#pragma unroll
+        for (int pp = 0; pp < PPW1; ++pp) wb[j * PPW1 + pp] = hl_ldnt8(gw + ((long long)j * PC1 + wave * PPW1 + pp) * 1024);
+      for (int j = 0; j < nlds; ++j)
+#pragma unroll
+        for (int pp = 0; pp < PPW1; ++pp)
+          hl_dma16<false, true>(smem + WT + (j * PC1 + wave * PPW1 + pp) * 1024,
+                                gw + ((long long)(NREG1 + j) * PC1 + wave * PPW1 + pp) * 1024);
+      // this wave's A-side DMA landed: behind it fly the NREG1 * PPW1 = 12 register
+      // loads + PPW1 = 3 DMAs per LDS tile (the exponent loads are older: waited for too)
+      if (nlds == 0) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else if (nlds == 1) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+    } else {
     const bf16* gw = hl_opaque(a.gu) + (long long)t0 * KC1 * 512 + ln * 8;
 #pragma unroll
     for (int j = 0; j < NREG1; ++j)
@@ -132,6 +210,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     if (nlds == 0) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
     else if (nlds == 1) asm volatile("s_waitcnt vmcnt(30)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
+    }
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the x columns landed
   }
@@ -158,15 +237,29 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     f32x4 acc[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float sc1[6];   // W8: 2^e of this lane's row of each tile slot
+#pragma unroll
+    for (int j = 0; j < 6; ++j) sc1[j] = W8 ? w8_scale(hl_vopaque(ex1[j])) : 0.f;
 #pragma unroll
     for (int kk = 0; kk < KPW1; ++kk) {
       const int kc = wave * KPW1 + kk;
       const bf16x8 av = *(const bf16x8*)(xs + (ln & 15) * XST + kc * 32 + 8 * (ln >> 4));
+      if constexpr (W8) {   // k-block kc = half kk & 1 of pair kc >> 1; the fragment = code * 2^e[row]
+#pragma unroll
+        for (int j = 0; j < NREG1; ++j)
+          acc[j] = mfma16(av, hl_frag8(wb[j * PPW1 + (kk >> 1)], kk & 1, sc1[j]), acc[j]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {   // (unfilled slots: products never stored)
+          const u32x2 v = *(const u32x2*)(smem + WT + (j * PC1 + (kc >> 1)) * 1024 + ln * 16 + 8 * (kk & 1));
+          acc[NREG1 + j] = mfma16(av, cvt8s(v[0], v[1], sc1[NREG1 + j]), acc[NREG1 + j]);
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < NREG1; ++j) acc[j] = mfma16(av, wb[j * KPW1 + kk], acc[j]);
 #pragma unroll
       for (int j = 0; j < 2; ++j)   // (unfilled slots: products never stored)
         acc[NREG1 + j] = mfma16(av, *(const bf16x8*)(wt_s + (j * KC1 + kc) * 512 + ln * 8), acc[NREG1 + j]);
+      }
     }
 #pragma unroll
     for (int j = 0; j < 6; ++j)
@@ -197,12 +290,40 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     // workgroup's 8 rows of each 1 KB block (512 B: lanes 0-31 block b, 32-63
     // block b + 1; the last pair's second block is padding)
     const int ln = hl_vopaque(lane);
+    if constexpr (W8) {
+      // k-blocks [c0, c0 + 18) as 8-byte fragments in wq.  Even waves: 9 whole
+      // pairs.  Odd waves start on a pair's second half: that half and the last
+      // k-block's first half as 8-byte loads, 8 whole pairs between (k_gemv's W8
+      // form, gemv_dev.h ldw8_chunks).  Lanes of the other half tile re-read the
+      // bytes of lane ^ 8 (no line of their own; their products are never stored).
+      const int lm = (ln & ~8) | 8 * (d & 1), c0 = wave * KPW2;
+      const unsigned char* dw = hl_opaque(a.dn8) + (long long)(d >> 1) * PC2 * 1024 + lm * 16;
+      if (c0 & 1) {   // wave-uniform
+        wq[0] = hl_ldnt8h(dw + (long long)(c0 >> 1) * 1024 + 8);
+#pragma unroll
+        for (int i = 0; i < (NREG2 - 2) / 2; ++i) {
+          const u32x4 v = hl_ldnt8(dw + (long long)(((c0 + 1) >> 1) + i) * 1024);
+          wq[1 + 2 * i] = (u32x2){v[0], v[1]};
+          wq[2 + 2 * i] = (u32x2){v[2], v[3]};
+        }
+        wq[NREG2 - 1] = hl_ldnt8h(dw + (long long)((c0 + NREG2 - 1) >> 1) * 1024);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NREG2 / 2; ++i) {
+          const u32x4 v = hl_ldnt8(dw + (long long)((c0 >> 1) + i) * 1024);
+          wq[2 * i] = (u32x2){v[0], v[1]};
+          wq[2 * i + 1] = (u32x2){v[2], v[3]};
+        }
+      }
+      issue_dn_lds8();
+    } else {
     const bf16* dw = hl_opaque(a.dn) + (long long)(d >> 1) * KC2 * 512;
     const bool mine = ((ln & 15) >> 3) == (d & 1);
 #pragma unroll
     for (int kk = 0; kk < NREG2; ++kk)
       wb[kk] = hl_ldnt(mine ? dw + (long long)(wave * KPW2 + kk) * 512 + ln * 8 : dw);
     issue_dn_lds();
+    }
   }
   if (ctl) {   // act[m][8 (t0 + j) .. + 8], written through
     for (int q = lane; q < nt * R * 2; q += 64) {
@@ -236,6 +357,27 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
     // stored); unconditional reads in groups of 5 ahead of their MFMAs (a guarded
     // read per k-block serialised 35 LDS round trips with the MFMAs: ~1.9 us)
     const bf16* ab = act_s + min(ln & 15, R - 1) * AST + wave * KPW2 * 32 + 8 * (ln >> 4);
+    if constexpr (W8) {
+      const float sc = w8_scale(hl_vopaque(ex2));
+      const int c0 = wave * KPW2;
+#pragma unroll
+      for (int k0 = 0; k0 < KPW2; k0 += 5) {
+        bf16x8 av[5];
+        u32x2 wv[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+          av[i] = *(const bf16x8*)(ab + (k0 + i) * 32);
+          const int c = c0 + k0 + i;   // k-block c = half c & 1 of pair c >> 1 (slot (c >> 1) - pl0)
+          if (k0 + i >= NREG2)
+            wv[i] = *(const u32x2*)(smem + DN2 + (wave * SLOT8 + (c >> 1) - pl0) * 512 + p * 16 + 8 * (c & 1));
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+          const u32x2 v = k0 + i < NREG2 ? wq[k0 + i] : wv[i];
+          acc = mfma16(av[i], cvt8s(v[0], v[1], sc), acc);
+        }
+      }
+    } else {
 #pragma unroll
     for (int k0 = 0; k0 < KPW2; k0 += 5) {
       bf16x8 av[5], wv[5];
@@ -246,6 +388,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
       }
 #pragma unroll
       for (int i = 0; i < 5; ++i) acc = mfma16(av[i], k0 + i < NREG2 ? wb[k0 + i] : wv[i], acc);
+    }
     }
     *(f32x4*)(red2 + wave * 256 + ln * 4) = acc;
   }
@@ -265,13 +408,22 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
 
 bool lm_ffn_fits(int H, int F, int R) {
   if (H != lf::H || F != lf::F || R < 1 || R > lf::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn, lf::NT, lf::TOTAL, lf::G);
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn<false>, lf::NT, lf::TOTAL, lf::G);
+  return ok;
+}
+bool lm_ffn_w8_fits(int H, int F, int R) {
+  if (H != lf::H || F != lf::F || R < 1 || R > lf::RMAX) return false;
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn<true>, lf::NT, lf::TOTAL, lf::G);
   return ok;
 }
 
+// the W8 form when the code pointers are set (all four, or it is an error)
 int launch_lm_ffn(const LmFfnArgs& a, hipStream_t st) {
-  if (!lm_ffn_fits(lf::H, lf::F, a.R) || a.ldx < lf::H) return 3;
-  hipLaunchKernelGGL(k_lm_ffn, dim3(lf::G), dim3(lf::NT), lf::TOTAL, st, a);
+  const bool w8 = a.gu8 != nullptr;
+  if (w8 && (!a.gue || !a.dn8 || !a.dne)) return 1;
+  if (!(w8 ? lm_ffn_w8_fits(lf::H, lf::F, a.R) : lm_ffn_fits(lf::H, lf::F, a.R)) || a.ldx < lf::H) return 3;
+  if (w8) hipLaunchKernelGGL(k_lm_ffn<true>, dim3(lf::G), dim3(lf::NT), lf::TOTAL, st, a);
+  else hipLaunchKernelGGL(k_lm_ffn<false>, dim3(lf::G), dim3(lf::NT), lf::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -314,8 +466,12 @@ constexpr int TOTAL = SM + SM_B;
 static_assert(RMAX * XST * 2 <= XS_B && TOTAL <= 160 * 1024, "lm ffn16 LDS");
 static_assert(G == pk::G && NG == pk::TICKETS && NR == pk::TICKET_STEP,
               "grid waits: 256 arrivals per wait; one ticket word per column group, one arrival per hidden range");
+// W8: a wave's 24 gate|up k-blocks are 12 whole pairs, its 14 down k-blocks 7 (even starts)
+constexpr int PC1 = KC1 / 2, PC2 = KC2 / 2, PH1 = KH1 / 2, PR = KR / 2, PW2 = KW2 / 2;
+static_assert(KH1 % 2 == 0 && KR % 2 == 0 && KW2 % 2 == 0, "lm ffn16 W8: whole pairs per wave");
 }  // namespace lf16
 
+template <bool W8>
 __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   using namespace lf16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -345,7 +501,16 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   auto stamp = [&](int k) { hl_stamp(a.stamps, w, k, 0); };
   stamp(0);
 
-  bf16x8 wb[KH1];
+  // W8: a lane's weight registers are its 16 code bytes of a pair block; the exponents of
+  // its row (lane & 15) of the gate|up tile and of the down tile are loaded here, ahead of
+  // the A side, so the vmcnt immediate below counts weight loads only
+  using WF = std::conditional_t<W8, u32x4, bf16x8>;
+  WF wb[W8 ? PH1 : KH1];
+  int ex1 = 0, ex2 = 0;
+  if constexpr (W8) {   // (unconditional, clamped: no branch to wait in; read through hl_vopaque where first used)
+    ex1 = a.gue[min(t0 + js, T1 - 1) * 16 + (lane & 15)];
+    ex2 = a.dne[(owner ? 2 * grp + (wave & 1) : 0) * 16 + (lane & 15)];
+  }
   if (!ctl) {
     const int ln = hl_vopaque(lane);
     // the A side first (rows m >= R re-read row R - 1: their products are never stored), the norm weight
@@ -355,10 +520,18 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
     }
     if (wave < 3) hl_dma16<false>(nw_s + wave * 512, hl_opaque(a.nw) + (wave * 64 + ln) * 8);
     if (busy1) {
+      if constexpr (W8) {
+        const unsigned char* gw = hl_opaque(a.gu8) + ((long long)(t0 + js) * PC1 + kh * PH1) * 1024 + ln * 16;
+#pragma unroll
+        for (int pp = 0; pp < PH1; ++pp) wb[pp] = hl_ldnt8(gw + (long long)pp * 1024);
+        // this wave's A-side DMA: behind it fly the PH1 = 12 pair loads (the exponent loads are older)
+        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      } else {
       const bf16* gw = hl_opaque(a.gu) + ((long long)(t0 + js) * KC1 + kh * KH1) * 512 + ln * 8;
 #pragma unroll
       for (int kk = 0; kk < KH1; ++kk) wb[kk] = hl_ldnt(gw + (long long)kk * 512);
       asm volatile("s_waitcnt vmcnt(24)" ::: "memory");   // this wave's A-side DMA (the 24 weight loads may fly)
+      }
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -383,9 +556,14 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   if (busy1) {   // gate|up tile t0 + js over this wave's K half
     const int ln = hl_vopaque(lane);
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float sc1 = W8 ? w8_scale(hl_vopaque(ex1)) : 0.f;   // W8: 2^e of this lane's row of the tile
 #pragma unroll
     for (int kk = 0; kk < KH1; ++kk) {
       const int kc = kh * KH1 + kk;
+      if constexpr (W8)
+        acc = mfma16(*(const bf16x8*)(xs + (ln & 15) * XST + kc * 32 + 8 * (ln >> 4)),
+                     hl_frag8(wb[kk >> 1], kk & 1, sc1), acc);
+      else
       acc = mfma16(*(const bf16x8*)(xs + (ln & 15) * XST + kc * 32 + 8 * (ln >> 4)), wb[kk], acc);
     }
     *(f32x4*)(red + (js * 2 + kh) * 256 + ln * 4) = acc;
@@ -419,9 +597,16 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
     // ~3.5 us): tile 2 grp + (v & 1), k-blocks [70 rng + 14 (v >> 1), + 14), into
     // the registers freed by gate|up
     const int ln = hl_vopaque(lane);
+    if constexpr (W8) {
+      const unsigned char* dw =
+          hl_opaque(a.dn8) + ((long long)(2 * grp + (wave & 1)) * PC2 + rng * PR + (wave >> 1) * PW2) * 1024 + ln * 16;
+#pragma unroll
+      for (int pp = 0; pp < PW2; ++pp) wb[pp] = hl_ldnt8(dw + (long long)pp * 1024);
+    } else {
     const bf16* dw = hl_opaque(a.dn) + ((long long)(2 * grp + (wave & 1)) * KC2 + rng * KR + (wave >> 1) * KW2) * 512 + ln * 8;
 #pragma unroll
     for (int kk = 0; kk < KW2; ++kk) wb[kk] = hl_ldnt(dw + (long long)kk * 512);
+    }
   }
   if (ctl && lane == 0) ok_s[0] = hl_poll(a.sync, pk::GEN_LM_FFN16, g0, pk::SHARDS, a.err) ? 1u : 0u;
   __syncthreads();
@@ -442,9 +627,14 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   if (wave < 10) {
     const int ln = hl_vopaque(lane);
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float sc2 = W8 ? w8_scale(hl_vopaque(ex2)) : 0.f;   // W8: 2^e of this lane's row of the down tile
 #pragma unroll
     for (int kk = 0; kk < KW2; ++kk) {
       const int kc = (wave >> 1) * KW2 + kk;
+      if constexpr (W8)
+        acc = mfma16(*(const bf16x8*)(xs + (ln & 15) * AST + kc * 32 + 8 * (ln >> 4)),
+                     hl_frag8(wb[kk >> 1], kk & 1, sc2), acc);
+      else
       acc = mfma16(*(const bf16x8*)(xs + (ln & 15) * AST + kc * 32 + 8 * (ln >> 4)), wb[kk], acc);
     }
     *(f32x4*)(red + ((wave & 1) * 5 + (wave >> 1)) * 256 + ln * 4) = acc;
@@ -484,12 +674,21 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
 
 bool lm_ffn16_fits(int H, int F, int R) {
   if (H != lf16::H || F != lf16::F || R < 3 || R > lf16::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16, lf16::NT, lf16::TOTAL, lf16::G);
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16<false>, lf16::NT, lf16::TOTAL, lf16::G);
+  return ok;
+}
+bool lm_ffn16_w8_fits(int H, int F, int R) {
+  if (H != lf16::H || F != lf16::F || R < 3 || R > lf16::RMAX) return false;
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16<true>, lf16::NT, lf16::TOTAL, lf16::G);
   return ok;
 }
 
 int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st) {
-  if (!lm_ffn16_fits(lf16::H, lf16::F, a.R) || a.ldx < lf16::H || !a.slab) return 3;
-  hipLaunchKernelGGL(k_lm_ffn16, dim3(lf16::G), dim3(lf16::NT), lf16::TOTAL, st, a);
+  const bool w8 = a.gu8 != nullptr;
+  if (w8 && (!a.gue || !a.dn8 || !a.dne)) return 1;
+  if (!(w8 ? lm_ffn16_w8_fits(lf16::H, lf16::F, a.R) : lm_ffn16_fits(lf16::H, lf16::F, a.R)) || a.ldx < lf16::H || !a.slab)
+    return 3;
+  if (w8) hipLaunchKernelGGL(k_lm_ffn16<true>, dim3(lf16::G), dim3(lf16::NT), lf16::TOTAL, st, a);
+  else hipLaunchKernelGGL(k_lm_ffn16<false>, dim3(lf16::G), dim3(lf16::NT), lf16::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

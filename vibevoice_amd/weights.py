@@ -232,6 +232,15 @@ def check_kv_dtype(kv_dtype, tp_size=1):
     return kv_dtype
 
 
+def _pow2(k):
+    """2.0 ** k (int tensor, -126 <= k <= 127) as float32, built from the exponent
+    bits: exact on every device.  (torch.ldexp multiplies by pow(2.0, k), which a
+    GPU may evaluate an ulp off for |k| >= 16 -- enough to flip the ties of the
+    e4m3 rounding, so a matrix packed on the GPU and fake_quantize_state_dict on
+    the CPU disagreed on rows with exponents <= -16.)"""
+    return ((k.to(torch.int32).clamp(-126, 127) + 127) << 23).view(torch.float32)
+
+
 def quantize_rows_e4m3(w):
     """[N, K] -> (codes [N, K] torch.float8_e4m3fn (OCP), e [N] int8) with
     w ~ codes * 2**e[n]: e[n] is the smallest integer with amax(row) / 2**e <= 448
@@ -243,13 +252,13 @@ def quantize_rows_e4m3(w):
     m, x = torch.frexp(amax)
     e = torch.where(m <= 0.875, x - 9, x - 8)
     e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(_E_MIN, 127)
-    codes = torch.ldexp(wf, -e[:, None]).to(torch.float8_e4m3fn)
+    codes = (wf * _pow2(-e)[:, None]).to(torch.float8_e4m3fn)
     return codes, e.to(torch.int8)
 
 
 def dequantize_rows(codes, e):
     """codes * 2**e[n] as bf16; exact (4 significant bits, a power-of-two scale)."""
-    return torch.ldexp(codes.float(), e.to(torch.int32)[:, None]).to(torch.bfloat16)
+    return (codes.float() * _pow2(e)[:, None]).to(torch.bfloat16)
 
 
 def fake_quantize_kv(x):
