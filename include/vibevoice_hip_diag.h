@@ -85,6 +85,25 @@ int vv_diag_kv_read(vv_ctx* ctx, int slot, int p0, int p1, void* k_out, void* v_
 int vv_diag_kv_write(vv_ctx* ctx, int slot, int p0, int p1, const void* k_in, const void* v_in);
 int vv_diag_attn_ctx(vv_ctx* ctx, int layer, int nq, const void* q, const int* slots, const int* pos, int form,
                      void* out, vv_stream st);
+/* Test hooks on the streaming codec's state: the per-slot conv buffers of one net
+ * (0 = acoustic decoder, 1 = semantic encoder, as vv_codec_reset_net), each
+ * [ctx history rows | rows of the last step][C], in allocation order: the stem,
+ * then per stage the transition before it (stages >= 1) and its Block1Ds' mixer
+ * buffers, then the head.
+ *   vv_diag_codec_layout: host only.  out[0] = the number of buffers, then per
+ *     buffer {kind (0 stem, 1 transition, 2 mixer, 3 head), stage, block, ctx, T,
+ *     rows, C}; n is the caller's capacity in words (fails, writing nothing, when
+ *     it is short).
+ *   vv_diag_codec_state: synchronises the device, then copies `slot`'s [rows][C]
+ *     slice of every buffer, back to back in layout order, into the device bf16
+ *     buffer out (fails, writing nothing, when capacity_elems is short).  Read
+ *     only: no kernel, no launch changes.
+ * After a vv_codec_step, in every stage form: rows [0, ctx) hold the history the
+ * next frame reads; a transition's (and the head's) rows [ctx, ctx + T) hold the
+ * previous stage's complete output; a mixer's rows [ctx + T - 6, ctx + T) its
+ * block's last normalised rows (the one-launch stage forms store no others). */
+int vv_diag_codec_layout(vv_ctx* ctx, int net, int* out, int n);
+int vv_diag_codec_state(vv_ctx* ctx, int net, int slot, void* out, int64_t capacity_elems);
 /* GQA attention of nq query rows (q [nq, nh*128] bf16, RoPE applied) over a
  * caller-owned cache in the engine layout ([slot][kv_head][ctx][128], strides
  * in elements): row i attends keys [0, pos[i]] of slot slots[i] -> out

@@ -7,6 +7,10 @@ frame (its state must not move), set_to_zero on speech_end, and the
 acoustic+semantic connector sum written into the next-embedding rows.
 Tolerance (bf16 model, 60+ layers deep, different GEMM accumulation order
 than the reference / oracle): rel L2 < 3e-2 and cosine > 0.999.
+
+A failure here says the chain is off; tests/test_gpu_codec_stages.py says which
+stage, block and slot (each stage against its own float64 reference, and the
+streaming state bit for bit).
 """
 import pytest
 import torch

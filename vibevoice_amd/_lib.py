@@ -132,6 +132,8 @@ EXPORTS = [
     ("vv_diag_kv_read", I, [P, I, I, I, P, P]),
     ("vv_diag_kv_write", I, [P, I, I, I, P, P]),
     ("vv_diag_attn_ctx", I, [P, I, I, P, P, P, I, P, P]),
+    ("vv_diag_codec_layout", I, [P, I, ctypes.POINTER(I), I]),
+    ("vv_diag_codec_state", I, [P, I, I, P, I64]),
 ]
 
 EPI = {"store": 0, "gelu": 1, "silu_mul": 2, "res": 3, "f32": 4}

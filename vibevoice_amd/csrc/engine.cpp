@@ -2608,6 +2608,58 @@ int vv_diag_kv_write(vv_ctx* c, int slot, int p0, int p1, const void* k_in, cons
   return diag_kv_rows(c, slot, p0, p1, const_cast<void*>(k_in), const_cast<void*>(v_in), 1, "vv_diag_kv_write");
 }
 
+// Diagnostics: the streaming codec's per-slot conv buffers (net 0 = acoustic decoder, 1 =
+// semantic encoder) in convnet_alloc's order: stem, per stage tr[i] (i > 0) and mix[i][0..depth),
+// head.  Layout: host only, out = {count, then {kind (0 stem, 1 transition, 2 mixer, 3 head),
+// stage, block, ctx, T, rows, C} per buffer}.  State: the slot's [rows][C] slice of every buffer,
+// back to back in that order, into a device bf16 buffer (synchronous; plain copies).
+struct CodecBufRef {
+  const ConvBuf* b;
+  int kind, stage, block;
+};
+static std::vector<CodecBufRef> codec_bufs(const ConvNet& n) {
+  std::vector<CodecBufRef> v;
+  v.push_back({&n.stem, 0, 0, 0});
+  for (int i = 0; i < n.nst; ++i) {
+    if (i > 0) v.push_back({&n.tr[i], 1, i, 0});
+    for (int j = 0; j < n.depth[i]; ++j) v.push_back({&n.mix[i][j], 2, i, j});
+  }
+  v.push_back({&n.head, 3, n.nst - 1, 0});
+  return v;
+}
+int vv_diag_codec_layout(vv_ctx* c, int net, int* out, int n) {
+  if (!c || !c->finalized || !out) FAIL("vv_diag_codec_layout: bad arguments");
+  if (net != 0 && net != 1) FAIL("vv_diag_codec_layout: net must be 0 (acoustic decoder) or 1 (semantic encoder)");
+  const std::vector<CodecBufRef> v = codec_bufs(net == 0 ? c->dec : c->sem);
+  if (n < 1 + 7 * (int)v.size()) FAIL("vv_diag_codec_layout: out[] too short (" + std::to_string(1 + 7 * v.size()) + " words)");
+  out[0] = (int)v.size();
+  int* o = out + 1;
+  for (const CodecBufRef& r : v) {
+    const int w[7] = {r.kind, r.stage, r.block, r.b->ctx, r.b->T, r.b->rows, r.b->C};
+    for (int k = 0; k < 7; ++k) *o++ = w[k];
+  }
+  return 0;
+}
+int vv_diag_codec_state(vv_ctx* c, int net, int slot, void* out, int64_t capacity_elems) {
+  if (!c || !c->finalized || !out) FAIL("vv_diag_codec_state: bad arguments");
+  if (net != 0 && net != 1) FAIL("vv_diag_codec_state: net must be 0 (acoustic decoder) or 1 (semantic encoder)");
+  const ConvNet& cn = net == 0 ? c->dec : c->sem;
+  if (slot < 0 || slot >= cn.slots) FAIL("vv_diag_codec_state: slot out of range");
+  const std::vector<CodecBufRef> v = codec_bufs(cn);
+  long long total = 0;
+  for (const CodecBufRef& r : v) total += r.b->sB;
+  if (capacity_elems < total) FAIL("vv_diag_codec_state: capacity short (" + std::to_string(total) + " elements)");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());
+  bf16* o = (bf16*)out;
+  for (const CodecBufRef& r : v) {
+    HIPCHK(hipMemcpy(o, r.b->base + (long long)slot * r.b->sB, (size_t)r.b->sB * sizeof(bf16), hipMemcpyDeviceToDevice));
+    o += r.b->sB;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+
 // Diagnostic: only the attention launch of `layer` over the context's own cache, no append:
 // nq query rows q [nq][n_heads * 128] (device) at (slots[i], pos[i]) (device tables; row i
 // attends keys [0, pos[i]]) -> out [nq][n_heads * 128].  form: 0 = the decode kernel as
