@@ -92,8 +92,9 @@ int vv_finalize(vv_ctx* ctx);
  * [N, K], weights.py:mfma_pack8 order) + <name>e (int8 [N], row scale 2^e);
  * vv_finalize names the tensor when neither or half a pair is bound.  Returns 1
  * when ctx holds quantised LM weights, else 0.  (The one-launch LM attention
- * kernel is then off; the one-launch MLP kernels run on the codes when every
- * gu_w / down_w is bound as FP8, on bf16 when none is, and are off for a mix.) */
+ * kernel is then off unless vv_set_lm_attn_w8; the one-launch MLP kernels run on
+ * the codes when every gu_w / down_w is bound as FP8, on bf16 when none is, and
+ * are off for a mix.) */
 int vv_weights_quantized(vv_ctx* ctx);
 /* KV cache format of the LM, per context: dtype 0 = bf16 (the default), 1 = FP8
  * (OCP e4m3): K (after RoPE) and V stored as one-byte codes in the bf16 cache's
@@ -112,6 +113,19 @@ int vv_weights_quantized(vv_ctx* ctx);
 int vv_set_kv_dtype(vv_ctx* ctx, int dtype);
 int vv_kv_dtype(vv_ctx* ctx);
 int vv_kv_bytes(vv_ctx* ctx, long long* bytes);
+/* The one-launch LM attention kernel on FP8 weights, per context: on = 1 runs
+ * k_lm_attn's W8 form (csrc/lm_attn.hip: the q|k|v and o_proj tiles read as e4m3
+ * codes + row exponents, bit for bit the bf16 kernel on the dequantised
+ * matrices) where every layer's qkv_w and o_w are bound as FP8 pairs and the
+ * kernel's other conditions hold (<= 16 decode rows, <= 4,096 keys, a bf16 KV
+ * cache, no tensor parallelism); on = 0 (the default) keeps an FP8 engine on the
+ * q|k|v, attention and o_proj launches.  A context whose qkv_w / o_w are all
+ * bf16 runs the bf16 form whatever the option; a mix of the two runs the three
+ * launches.  Callable after vv_create and before vv_finalize; later calls and
+ * values other than 0 / 1 are errors.
+ *   vv_lm_attn_w8: the context's option (0 / 1) */
+int vv_set_lm_attn_w8(vv_ctx* ctx, int on);
+int vv_lm_attn_w8(vv_ctx* ctx);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

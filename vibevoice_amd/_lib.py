@@ -40,6 +40,8 @@ EXPORTS = [
     ("vv_set_kv_dtype", I, [P, I]),
     ("vv_kv_dtype", I, [P]),
     ("vv_kv_bytes", I, [P, ctypes.POINTER(ctypes.c_longlong)]),
+    ("vv_set_lm_attn_w8", I, [P, I]),
+    ("vv_lm_attn_w8", I, [P]),
     ("vv_set_schedule", I, [P, I, ctypes.POINTER(F), P, P]),
     ("vv_lm_forward", I, [P, I, P, I, P, P, I, I, P, P, P, P]),
     ("vv_kv_copy", I, [P, I, P, P, P, P]),

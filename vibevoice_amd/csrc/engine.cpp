@@ -242,6 +242,11 @@ struct vv_ctx {
   // one-launch MLP kernels read one form throughout, a mixed binding keeps the GEMV pair
   enum { MLP_BF16 = 0, MLP_W8 = 1, MLP_MIXED = 2 };
   int mlp_form = MLP_BF16;
+  // the attention projections (qkv_w, o_w of every layer), decided the same way: k_lm_attn reads
+  // one form throughout (MLP_* values).  Its W8 form is this context's option
+  // (vv_set_lm_attn_w8 before vv_finalize, default off: an FP8 engine runs the three launches)
+  int attn_form = MLP_BF16;
+  int lm_attn_w8 = 0;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
   // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
   // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
@@ -1029,6 +1034,14 @@ int vv_set_kv_dtype(vv_ctx* c, int dtype) {
   return 0;
 }
 int vv_kv_dtype(vv_ctx* c) { return c ? c->kv_dtype : 0; }
+int vv_set_lm_attn_w8(vv_ctx* c, int on) {
+  if (on != 0 && on != 1) FAIL("vv_set_lm_attn_w8: unsupported value " + std::to_string(on) + " (0 = off, 1 = on)");
+  if (!c) FAIL("vv_set_lm_attn_w8: null context");
+  if (c->finalized) FAIL("vv_set_lm_attn_w8 after vv_finalize: the attention half's kernels are already chosen");
+  c->lm_attn_w8 = on;
+  return 0;
+}
+int vv_lm_attn_w8(vv_ctx* c) { return c ? c->lm_attn_w8 : 0; }
 int vv_kv_bytes(vv_ctx* c, long long* bytes) {
   if (!c || !bytes) FAIL("vv_kv_bytes: null argument");
   if (!c->finalized) FAIL("vv_kv_bytes before vv_finalize: the KV cache is not allocated yet");
@@ -1071,6 +1084,9 @@ int vv_finalize(vv_ctx* c) {
     int n8 = 0;
     for (const LmLayerW& w : c->lmw) n8 += (w.gu.w8 != nullptr) + (w.down.w8 != nullptr);
     c->mlp_form = n8 == 0 ? vv_ctx::MLP_BF16 : n8 == 2 * k.n_layers ? vv_ctx::MLP_W8 : vv_ctx::MLP_MIXED;
+    int a8 = 0;
+    for (const LmLayerW& w : c->lmw) a8 += (w.qkv.w8 != nullptr) + (w.o.w8 != nullptr);
+    c->attn_form = a8 == 0 ? vv_ctx::MLP_BF16 : a8 == 2 * k.n_layers ? vv_ctx::MLP_W8 : vv_ctx::MLP_MIXED;
   }
   if (c->quantized) {
     // the fallback's scratch (launch_gemm: more than 16 rows, forms k_gemv_w8 does not
@@ -1141,7 +1157,10 @@ int vv_finalize(vv_ctx* c) {
       mlp_one && (mlp_w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, 16) : lm_ffn16_fits(k.hidden, k.intermediate, 16));
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
   const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, LA_MAX_KEYS);
-  const bool la_fits = lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys) &&
+  // (the W8 form's own residency where this context will run it: codes throughout + its option)
+  const bool la_w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
+  const bool la_fits = (la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
+                              : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
@@ -1459,10 +1478,15 @@ extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launche
 }
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  return g_lm_attn && !c->quantized && !c->kv_dtype && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
+  // every layer's qkv_w and o_w bound as bf16, or as codes with the context's option on (the W8
+  // form: its own residency); a mixed binding, or codes without the option: the three launches
+  const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
+  if (c->attn_form != vv_ctx::MLP_BF16 && !w8) return false;
+  return g_lm_attn && !c->kv_dtype && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, LA_MAX_KEYS) &&
-         lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
+         (w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
+             : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)) &&
          lm_attn_part_floats(P.ntok, P.maxp) * sizeof(float) <= c->la_part.bytes && persist_on(c);
 }
 extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
@@ -1514,7 +1538,9 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       a.scale = 1.0f / sqrtf((float)d);
       a.R = P.ntok;
       a.ow = w.o.w;
-      a.res = l == 0 ? P.in_m : P.hm;
+      a.ow8 = w.o.w8;     // codes throughout: the launcher picks the W8 form (a.qkv carries q|k|v's)
+      a.owe = w.o.w8e;
+      a.res =l == 0 ? P.in_m : P.hm;
       a.out = P.hm;
       a.att = P.att;
       a.part = (float*)c->la_part.p;

@@ -340,8 +340,14 @@ struct LmAttnArgs {
                             // and attention rows of the R rows only (not 16); 2 = o_proj weights
                             // issued after the first wait, not at entry; 4 = o_proj's residual
                             // operand loaded at entry
+  // FP8 weights (the W8 form, run when the code pointers are set: qkv.w8 / qkv.w8e as gemm_args
+  // fills them, and these; qkv.w / ow are then unused): e4m3 codes in mfma_pack8 order + one int8
+  // exponent per packed row -- bit for bit the bf16 form on the dequantised matrices
+  const unsigned char* ow8;     // o_proj codes [H][H]
+  const signed char* owe;       // [H]
 };
 bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys);
+bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys);   // the W8 form's own residency
 size_t lm_attn_part_floats(int R, int keys);
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st);
 

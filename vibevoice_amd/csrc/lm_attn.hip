@@ -30,12 +30,25 @@
 // use sc1 / nt loads (L1-bypassing; MI355X_MICROARCH.md's hand-off table, first
 // row).  Arithmetic: epi_rope's and k_attn's (scores scaled after the MFMA, P
 // rounded to bf16 for P.V, l in fp32), the units merged as k_attn merges splits.
+//
+// W8 (the second instantiation; GemmArgs::w8 / w8e of LmAttnArgs::qkv, LmAttnArgs::ow8 /
+// owe): the two weight tiles are e4m3 codes in mfma_pack8 order (gemv_w8.hip: 1 KB pair
+// blocks of 16 rows x 64 columns = two k-blocks, a lane's 16 bytes = its two fragments) +
+// one int8 exponent per packed row.  Same workgroup roles, same 6 k-blocks per wave (3
+// whole pairs), same MFMA order per accumulator, same LDS sums, epilogues, phases 2-3,
+// waits and stamps; only the weight loads change: a lane holds 3 u32x4 per matrix instead
+// of 6 bf16x8 and converts a fragment to code * 2^e[row] (cvt8s: the bf16 value
+// k_dequant_w8 stores, exactly) where the bf16 form reads the register -- bit for bit the
+// bf16 kernel on the dequantised matrices (tests/test_gpu_w8_lm_attn.py).
+#include <type_traits>
+
 #include "persist_dev.h"
 
 namespace la {
 constexpr int H = 1536, NH = 12, NKV = 2, G = 6, D = 128, NQKV = (NH + 2 * NKV) * D;
 constexpr int GRID = pk::G, NW = 8, NT = NW * 64, RMAX = 16;
 constexpr int KC = H / 32, KPW = KC / NW;        // 48 k-blocks, 6 per wave
+constexpr int PC = KC / 2, PPW = KPW / 2;        // W8: 24 pair blocks per tile, 3 per wave
 constexpr int TQ = NQKV / 16, TO = H / 16;       // 128 q|k|v tiles, 96 o_proj tiles
 constexpr int O0 = TQ;                           // o_proj workgroups [O0, O0 + TO)
 constexpr int XST = H + 8;                       // padded LDS row (elements)
@@ -49,10 +62,12 @@ constexpr int TOTAL = (SM + SM_B) > 82 * 1024 ? (SM + SM_B) : 82 * 1024;
 constexpr int PART = G * D + 2 * G;              // floats per unit partial: O[6][128], then (m, l) x 6
 static_assert(SM + SM_B <= 160 * 1024, "lm attn LDS");
 static_assert(GRID == pk::G, "grid waits: 256 arrivals per wait");
+static_assert(KPW * NW == KC && KPW % 2 == 0 && PPW * 2 == KPW, "lm attn W8: a wave's k-blocks are whole pairs");
 }  // namespace la
 
 DEV void la_stamp(const LmAttnArgs& a, int k) { hl_stamp(a.stamps, blockIdx.x, k, 0); }
 
+template <bool W8>
 __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   using namespace la;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -85,7 +100,17 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     rv_pre = *(const bf16x4*)(rm_bf(a.res, r16) + 16 * (w - O0) + 4 * g4);
 
   // ================= phase 1: q|k|v tile (workgroups < 128) / o_proj weights (128..223)
-  bf16x8 wq[KPW], wo[KPW];
+  // W8: a lane's weight registers are its 16 code bytes of a pair block; the exponent of its
+  // row (lane & 15) of this workgroup's tile (q|k|v or o_proj) is loaded here, ahead of the A
+  // side, so the vmcnt immediate below counts weight loads only
+  using WF = std::conditional_t<W8, u32x4, bf16x8>;
+  constexpr int NWL = W8 ? PPW : KPW;   // weight loads per wave and matrix: one per register
+  WF wq[NWL], wo[NWL];
+  static_assert(sizeof(wq) == NWL * 16 && NWL * (W8 ? 64 : 32) == KPW * 32 && NWL <= 63,
+                "one 16-byte load per weight register, together the wave's 6 k-blocks; the count fits vmcnt");
+  int ex = 0;
+  if constexpr (W8)   // (unconditional, clamped: no branch to wait in; read through hl_vopaque where first used)
+    ex = ot ? a.owe[16 * (w - O0) + r16] : a.qkv.w8e[16 * min(w, TQ - 1) + r16];
   const int ln = hl_vopaque(lane);
   // wave 0's RoPE epilogue operands (row m = lane & 15, columns 16 w + 4 g ..): position,
   // slot and bias first, the cos / sin row (dependent on the position) after the weights
@@ -104,19 +129,32 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
       hl_dma16<false>(xs + m * XST + i * 512, rm_bf(a.qkv.a, min(m, R - 1)) + (i * 64 + ln) * 8);
     }
     if (wave < 3) hl_dma16<false>(nw_s + wave * 512, a.nw + (wave * 64 + ln) * 8);
+    if constexpr (W8) {   // this wave's 6 k-blocks = pairs [3 wave, + 3) of tile w
+      const unsigned char* wp = hl_opaque(a.qkv.w8) + ((long long)w * PC + wave * PPW) * 1024 + ln * 16;
+#pragma unroll
+      for (int pp = 0; pp < PPW; ++pp) wq[pp] = hl_ldnt8(wp + (long long)pp * 1024);
+    } else {
     const bf16* wp = hl_opaque(a.qkv.w) + ((long long)w * KC + wave * KPW) * 512 + ln * 8;
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) wq[kk] = hl_ldnt(wp + (long long)kk * 512);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // this wave's A-side DMA (KPW = 6 weight loads younger)
+    }
+    // this wave's A-side DMA: the NWL weight loads (6; W8: 3 -- its exponent load is older) are younger
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWL) : "memory");
     if (wave == 0 && RP.cs_tab) {
       const int j = 8 * (w & 7) + 4 * (g4 & 1);
       cs4 = *(const bf16x4*)(RP.cs_tab + (long long)rp * D + j);
       sn4 = *(const bf16x4*)(RP.cs_tab + (long long)rp * D + 64 + j);
     }
   } else if (ot && !(a.variant & 2)) {
+    if constexpr (W8) {
+      const unsigned char* wp = hl_opaque(a.ow8) + ((long long)(w - O0) * PC + wave * PPW) * 1024 + ln * 16;
+#pragma unroll
+      for (int pp = 0; pp < PPW; ++pp) wo[pp] = hl_ldnt8(wp + (long long)pp * 1024);
+    } else {
     const bf16* wp = hl_opaque(a.ow) + ((long long)(w - O0) * KC + wave * KPW) * 512 + ln * 8;
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) wo[kk] = hl_ldnt(wp + (long long)kk * 512);
+    }
   }
   if (threadIdx.x < 2 * RMAX) pre[threadIdx.x + 1] = nunit;
   __syncthreads();
@@ -142,9 +180,13 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     __syncthreads();
     // D[n][m]: A = the weight tile (row n = lane & 15), B = the A rows (column m)
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float sc = W8 ? w8_scale(hl_vopaque(ex)) : 0.f;   // W8: 2^e of this lane's row of the tile
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) {
-      const int kc = wave * KPW + kk;
+      const int kc = wave * KPW + kk;   // W8: k-block kc = half kk & 1 of pair kc >> 1
+      if constexpr (W8)
+        acc = mfma16(hl_frag8(wq[kk >> 1], kk & 1, sc), *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
+      else
       acc = mfma16(wq[kk], *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
     }
     *(f32x4*)(red + wave * 256 + lane * 4) = acc;
@@ -209,9 +251,15 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   la_stamp(a, 3);
   if (!ok_s[0]) return;
   if (ot && (a.variant & 2)) {
+    if constexpr (W8) {
+      const unsigned char* wp = hl_opaque(a.ow8) + ((long long)(w - O0) * PC + wave * PPW) * 1024 + ln * 16;
+#pragma unroll
+      for (int pp = 0; pp < PPW; ++pp) wo[pp] = hl_ldnt8(wp + (long long)pp * 1024);
+    } else {
     const bf16* wp = hl_opaque(a.ow) + ((long long)(w - O0) * KC + wave * KPW) * 512 + ln * 8;
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) wo[kk] = hl_ldnt(wp + (long long)kk * 512);
+    }
   }
 
   // ================= phase 2: attention units (row, kv head, 32 keys), one wave each
@@ -374,9 +422,13 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   __syncthreads();
   {
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float sc = W8 ? w8_scale(hl_vopaque(ex)) : 0.f;
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) {
       const int kc = wave * KPW + kk;
+      if constexpr (W8)
+        acc = mfma16(hl_frag8(wo[kk >> 1], kk & 1, sc), *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
+      else
       acc = mfma16(wo[kk], *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
     }
     *(f32x4*)(red + wave * 256 + lane * 4) = acc;
@@ -402,16 +454,27 @@ bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys) {
   if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D || R < 1 || R > la::RMAX || keys < 1 ||
       keys > LA_MAX_KEYS)
     return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_attn, la::NT, la::TOTAL, la::GRID);
+  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false>, la::NT, la::TOTAL, la::GRID);
+  return ok;
+}
+bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys) {
+  if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D || R < 1 || R > la::RMAX || keys < 1 ||
+      keys > LA_MAX_KEYS)
+    return false;
+  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<true>, la::NT, la::TOTAL, la::GRID);
   return ok;
 }
 
 size_t lm_attn_part_floats(int R, int keys) { return (size_t)R * la::NKV * ((keys + 31) / 32) * la::PART; }
 
+// the W8 form when a code pointer is set (all four of q|k|v's and o_proj's codes and exponents, or it is an error)
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st) {
-  if (!lm_attn_fits(la::H, la::NH, la::NKV, la::D, a.R, keys) || a.qkv.M != a.R || a.qkv.N != la::NQKV ||
-      a.qkv.K != la::H || !a.qkv.epi.bias || !a.part || !a.att || !a.sync || !a.err)
+  const bool w8 = a.qkv.w8 || a.qkv.w8e || a.ow8 || a.owe;
+  if (w8 && (!a.qkv.w8 || !a.qkv.w8e || !a.ow8 || !a.owe)) return 1;
+  if (!(w8 ? lm_attn_w8_fits(la::H, la::NH, la::NKV, la::D, a.R, keys) : lm_attn_fits(la::H, la::NH, la::NKV, la::D, a.R, keys)) ||
+      a.qkv.M != a.R || a.qkv.N != la::NQKV || a.qkv.K != la::H || !a.qkv.epi.bias || !a.part || !a.att || !a.sync || !a.err)
     return 3;
-  hipLaunchKernelGGL(k_lm_attn, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
+  if (w8) hipLaunchKernelGGL(k_lm_attn<true>, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
+  else hipLaunchKernelGGL(k_lm_attn<false>, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

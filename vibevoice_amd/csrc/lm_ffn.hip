@@ -38,15 +38,7 @@
 
 #include "persist_dev.h"
 
-// the FP8 weight stream: global and non-temporal as hl_ldnt; 16 bytes = a lane's
-// piece of a pair block, 8 bytes = one k-block's fragment of it
-typedef __attribute__((address_space(1))) const u32x4 hl_gu32x4;
-typedef __attribute__((address_space(1))) const u32x2 hl_gu32x2;
-DEV u32x4 hl_ldnt8(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x4*)p); }
-DEV u32x2 hl_ldnt8h(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x2*)p); }
-// fragment `half` (0 / 1) of a lane's 16 code bytes, scaled by the lane's row scale
-DEV bf16x8 hl_frag8(u32x4 v, int half, float sc) { return half ? cvt8s(v[2], v[3], sc) : cvt8s(v[0], v[1], sc); }
-
+// (the FP8 weight stream's loads and fragment conversion: persist_dev.h hl_ldnt8 / hl_ldnt8h / hl_frag8)
 namespace lf {
 constexpr int H = 1536, F = 8960, G = pk::G, RMAX = 2;
 constexpr int NTC = 512, NT = NTC + 64;   // 8 compute waves + the control wave

@@ -15,6 +15,14 @@ DEV bf16x8 hl_ld(const bf16* p) { return *(hl_gbf16x8*)p; }
 // a weight-stream load: global (a flat load would also count in lgkmcnt, so every
 // LDS wait would drain the stream) and non-temporal (gemv_dev.h ldw)
 DEV bf16x8 hl_ldnt(const bf16* p) { return __builtin_nontemporal_load((hl_gbf16x8*)p); }
+// the FP8 weight stream (lm_ffn.hip, lm_attn.hip): global and non-temporal as hl_ldnt;
+// 16 bytes = a lane's piece of a pair block, 8 bytes = one k-block's fragment of it
+typedef __attribute__((address_space(1))) const u32x4 hl_gu32x4;
+typedef __attribute__((address_space(1))) const u32x2 hl_gu32x2;
+DEV u32x4 hl_ldnt8(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x4*)p); }
+DEV u32x2 hl_ldnt8h(const unsigned char* p) { return __builtin_nontemporal_load((hl_gu32x2*)p); }
+// fragment `half` (0 / 1) of a lane's 16 code bytes, scaled by the lane's row scale
+DEV bf16x8 hl_frag8(u32x4 v, int half, float sc) { return half ? cvt8s(v[2], v[3], sc) : cvt8s(v[0], v[1], sc); }
 
 DEV float hl_dot8(bf16x8 w, bf16x8 x, float acc) {
   acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(w, w, 0, 1), __builtin_shufflevector(x, x, 0, 1), acc, false);

@@ -10,7 +10,8 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import W8_CODES, check_kv_dtype, check_weight_dtype, codec_channels, head_tp_check, pack
+from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
+                      pack)
 
 _VALID_IDS_DEFAULT = None
 
@@ -76,7 +77,7 @@ class Engine:
 
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
-                 persistent=True, weight_dtype=None, kv_dtype=None):
+                 persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -94,10 +95,16 @@ class Engine:
         OCP e4m3 codes + a power-of-two scale per row (weights.pack; tp_size 1
         only).  With `packed`, the format is the one those weights were packed in.
         kv_dtype: None = a bf16 KV cache; "fp8_e4m3" = K and V stored as OCP e4m3
-        codes + a power-of-two scale per cached row (vv_set_kv_dtype; tp_size 1 only)."""
+        codes + a power-of-two scale per cached row (vv_set_kv_dtype; tp_size 1 only).
+        lm_attn_w8: True runs the one-launch LM attention kernel on the FP8 codes
+        (vv_set_lm_attn_w8; default off: an FP8 engine runs the q|k|v, attention and
+        o_proj launches).  Needs FP8 weights, a bf16 KV cache and tp_size 1."""
         persistent = normalize_persistent(persistent)
         check_weight_dtype(weight_dtype, tp_size)
         check_kv_dtype(kv_dtype, tp_size)
+        packed_fp8 = packed is not None and any(k.endswith("_w" + W8_CODES) for k in packed)
+        self.lm_attn_w8 = check_lm_attn_w8(lm_attn_w8, weight_dtype if packed is None else "fp8_e4m3" if packed_fp8 else None,
+                                           kv_dtype, tp_size)
         self.kv_dtype = kv_dtype
         L = _lib.lib()
         self.cfg = cfg
@@ -134,6 +141,8 @@ class Engine:
                 _lib.check(L.vv_set_persistent(h, 2 if persistent == "follow" else 0), "set_persistent")
             if kv_dtype is not None:
                 _lib.check(L.vv_set_kv_dtype(h, 1), "set_kv_dtype")
+            if self.lm_attn_w8:
+                _lib.check(L.vv_set_lm_attn_w8(h, 1), "set_lm_attn_w8")
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")

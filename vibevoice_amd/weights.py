@@ -232,6 +232,24 @@ def check_kv_dtype(kv_dtype, tp_size=1):
     return kv_dtype
 
 
+def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1):
+    """The per-engine option that runs the one-launch LM attention kernel on FP8
+    weights (vv_set_lm_attn_w8): it needs FP8 weights (`weight_dtype` is the
+    format the weights are, or were, packed in), a bf16 KV cache and tp_size 1."""
+    if lm_attn_w8 not in (False, True, 0, 1):
+        raise ValueError(f"lm_attn_w8={lm_attn_w8!r}: expected True or False")
+    if lm_attn_w8:
+        if weight_dtype != "fp8_e4m3":
+            raise ValueError("lm_attn_w8=True needs FP8 weights (weight_dtype='fp8_e4m3'); "
+                             f"this engine's are {weight_dtype or 'bf16'}")
+        if kv_dtype is not None:
+            raise ValueError(f"lm_attn_w8=True is not supported with kv_dtype={kv_dtype!r}: "
+                             "the one-launch attention kernel reads a bf16 KV cache")
+        if tp_size > 1:
+            raise ValueError(f"lm_attn_w8=True is not supported with tensor parallelism (tp_size={tp_size})")
+    return bool(lm_attn_w8)
+
+
 def _pow2(k):
     """2.0 ** k (int tensor, -126 <= k <= 127) as float32, built from the exponent
     bits: exact on every device.  (torch.ldexp multiplies by pow(2.0, k), which a
