@@ -105,7 +105,7 @@ int vv_weights_quantized(vv_ctx* ctx);
  * (csrc/kv_fp8.hip).  Callable after vv_create and before vv_finalize, which
  * allocates the cache; later calls, other values and tensor-parallel engines
  * are errors.  Under FP8 KV the one-launch LM attention kernel is off
- * (vv_lm_attn_active reports 0).
+ * (vv_lm_attn_active reports 0) unless vv_set_lm_attn_kv8.
  *   vv_kv_dtype: the context's format (0 / 1)
  *   vv_kv_bytes: *bytes = device bytes of the finalized context's KV cache,
  *     exponents included, the append staging excluded (an error before
@@ -118,7 +118,7 @@ int vv_kv_bytes(vv_ctx* ctx, long long* bytes);
  * codes + row exponents, bit for bit the bf16 kernel on the dequantised
  * matrices) where every layer's qkv_w and o_w are bound as FP8 pairs and the
  * kernel's other conditions hold (<= 16 decode rows, <= 4,096 keys, a bf16 KV
- * cache, no tensor parallelism); on = 0 (the default) keeps an FP8 engine on the
+ * cache or vv_set_lm_attn_kv8, no tensor parallelism); on = 0 (the default) keeps an FP8 engine on the
  * q|k|v, attention and o_proj launches.  A context whose qkv_w / o_w are all
  * bf16 runs the bf16 form whatever the option; a mix of the two runs the three
  * launches.  Callable after vv_create and before vv_finalize; later calls and
@@ -126,6 +126,20 @@ int vv_kv_bytes(vv_ctx* ctx, long long* bytes);
  *   vv_lm_attn_w8: the context's option (0 / 1) */
 int vv_set_lm_attn_w8(vv_ctx* ctx, int on);
 int vv_lm_attn_w8(vv_ctx* ctx);
+/* The one-launch LM attention kernel on an FP8 KV cache, per context; off unless
+ * set.  on = 1 runs k_lm_attn's FP8-KV form (csrc/lm_attn.hip: the pass's K / V
+ * rows go through the cache's e4m3 row quantiser inside the launch, the
+ * attention reads codes + row exponents; no k_kv_quant launch) where the context
+ * has an FP8 KV cache (vv_set_kv_dtype 1) and the kernel's other conditions hold
+ * (<= 16 decode rows, <= 4,096 keys, no tensor parallelism; qkv_w / o_w all bf16,
+ * or all FP8 pairs with vv_set_lm_attn_w8); on = 0 (the default) keeps an FP8-KV
+ * engine on the q|k|v, quantise, attention and o_proj launches.  It stores the
+ * codes and exponents those launches store.  Without an FP8 KV cache the option
+ * has no effect.  Callable after vv_create and before vv_finalize; later calls
+ * and values other than 0 / 1 are errors.
+ *   vv_lm_attn_kv8: the context's option (0 / 1) */
+int vv_set_lm_attn_kv8(vv_ctx* ctx, int on);
+int vv_lm_attn_kv8(vv_ctx* ctx);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

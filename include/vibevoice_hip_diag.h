@@ -230,6 +230,12 @@ int vv_head_fin_active(vv_ctx* ctx, int n);
 int vv_lm_attn(int on);
 int vv_lm_attn_active(vv_ctx* ctx, int ntok, int max_pos_p1);
 int vv_lm_attn_stamps(void* buf);
+/* Diagnostic switch: a bf16-weight, bf16-KV context runs the one-launch LM
+ * attention kernel's round-trip form (k_lm_attn<false, 2>: the FP8-KV form's data
+ * flow and e4m3 row quantiser, the appended rows stored dequantised in the bf16
+ * cache and read as bf16) where it would run the plain form (1), or the plain
+ * form (0, default) -- the bits the FP8-KV form must produce. */
+int vv_lm_attn_kvround(int on);
 /* Diagnostic (bench.py): `reps` passes over the LM layers' attention halves alone
  * on ntok decode rows (embeds [ntok][H] as layer 0's input, slots / positions as
  * for vv_lm_forward). */

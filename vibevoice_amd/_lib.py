@@ -42,6 +42,8 @@ EXPORTS = [
     ("vv_kv_bytes", I, [P, ctypes.POINTER(ctypes.c_longlong)]),
     ("vv_set_lm_attn_w8", I, [P, I]),
     ("vv_lm_attn_w8", I, [P]),
+    ("vv_set_lm_attn_kv8", I, [P, I]),
+    ("vv_lm_attn_kv8", I, [P]),
     ("vv_set_schedule", I, [P, I, ctypes.POINTER(F), P, P]),
     ("vv_lm_forward", I, [P, I, P, I, P, P, I, I, P, P, P, P]),
     ("vv_kv_copy", I, [P, I, P, P, P, P]),
@@ -100,6 +102,7 @@ EXPORTS = [
     ("vv_head_fin", I, [I]),
     ("vv_head_fin_active", I, [P, I]),
     ("vv_lm_attn", I, [I]),
+    ("vv_lm_attn_kvround", I, [I]),
     ("vv_lm_attn_active", I, [P, I, I]),
     ("vv_lm_attn_stamps", I, [P]),
     ("vv_lm_attn_replay", I, [P, I, P, P, P, I, I, P]),

@@ -247,6 +247,10 @@ struct vv_ctx {
   // (vv_set_lm_attn_w8 before vv_finalize, default off: an FP8 engine runs the three launches)
   int attn_form = MLP_BF16;
   int lm_attn_w8 = 0;
+  // ... and its FP8-KV form (k_lm_attn<., 1>: the rows quantised inside the launch) is this
+  // context's option too (vv_set_lm_attn_kv8 before vv_finalize, default off: an FP8-KV engine
+  // runs q|k|v, k_kv_quant, k_attn, o_proj)
+  int lm_attn_kv8 = 0;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
   // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
   // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
@@ -255,7 +259,9 @@ struct vv_ctx {
   KV8 kv8 = {nullptr, nullptr, nullptr, nullptr};
   // the staged append of a pass: a one-slot bf16 cache over the pass's token indices
   // (K | V), the cos / sin rows of the tokens' real positions, and the slot (all 0) /
-  // position (0, 1, ...) tables the q|k|v epilogue indexes it with
+  // position (0, 1, ...) tables the q|k|v epilogue indexes it with.  (Every engine has the
+  // decode-pass-sized one: k_lm_attn's KVQ forms stage their rows in it, the diagnostic
+  // round trip vv_lm_attn_kvround on a bf16 cache included; it is no part of vv_kv_bytes.)
   DevBuf kv_stage;
   size_t kv_stage_tokens = 0;
   KVLayout stg = {nullptr, nullptr, 0, 0, 0, 0, 0};
@@ -300,7 +306,7 @@ static int need_lm_w(vv_ctx* c, const std::string& n, int64_t N, int64_t K, LmW*
   return 0;
 }
 
-// FP8 KV: the staging cache for passes of up to ntok tokens (grown outside a hot
+// The staging cache for passes of up to ntok tokens (FP8 KV; grown outside a hot
 // call only: vv_finalize sizes it for a decode pass, a longer prefill grows it and
 // bumps the workspace epoch through DevBuf::ensure)
 static int kv_stage_ensure(vv_ctx* c, size_t ntok) {
@@ -1042,6 +1048,14 @@ int vv_set_lm_attn_w8(vv_ctx* c, int on) {
   return 0;
 }
 int vv_lm_attn_w8(vv_ctx* c) { return c ? c->lm_attn_w8 : 0; }
+int vv_set_lm_attn_kv8(vv_ctx* c, int on) {
+  if (on != 0 && on != 1) FAIL("vv_set_lm_attn_kv8: unsupported value " + std::to_string(on) + " (0 = off, 1 = on)");
+  if (!c) FAIL("vv_set_lm_attn_kv8: null context");
+  if (c->finalized) FAIL("vv_set_lm_attn_kv8 after vv_finalize: the attention half's kernels are already chosen");
+  c->lm_attn_kv8 = on;
+  return 0;
+}
+int vv_lm_attn_kv8(vv_ctx* c) { return c ? c->lm_attn_kv8 : 0; }
 int vv_kv_bytes(vv_ctx* c, long long* bytes) {
   if (!c || !bytes) FAIL("vv_kv_bytes: null argument");
   if (!c->finalized) FAIL("vv_kv_bytes before vv_finalize: the KV cache is not allocated yet");
@@ -1158,9 +1172,12 @@ int vv_finalize(vv_ctx* c) {
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
   const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, LA_MAX_KEYS);
   // (the W8 form's own residency where this context will run it: codes throughout + its option)
+  // (... and the FP8-KV form's where an FP8-KV context's option selects it)
   const bool la_w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
-  const bool la_fits = (la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
-                              : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)) &&
+  const bool la_kv8 = c->kv_dtype && c->lm_attn_kv8;
+  const bool la_fits = (la_kv8  ? lm_attn_kvq_fits(la_w8, 1, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
+                        : la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
+                                : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
@@ -1206,11 +1223,11 @@ int vv_finalize(vv_ctx* c) {
     c->kv8.v = (unsigned char*)c->kv8_v.p;
     c->kv8.ek = (signed char*)c->kv8_ek.p;
     c->kv8.ev = (signed char*)c->kv8_ev.p;
-    CHK(kv_stage_ensure(c, (size_t)c->lm_slots));
   } else {
     CHK(c->kv_k.ensure(kvb));
     CHK(c->kv_v.ensure(kvb + 256));
   }
+  if (d == 128) CHK(kv_stage_ensure(c, (size_t)c->lm_slots));   // a decode pass's staging (>= 32 positions)
   // RoPE cos / sin per position (the q|k|v epilogue reads it instead of cosf / sinf)
   if (d == 128) {
     CHK(c->rope_tab.ensure((size_t)c->kv.max_ctx * 128 * sizeof(bf16)));
@@ -1472,21 +1489,37 @@ extern "C" int vv_lm_attn(int on) {
   g_lm_attn = on & 15;   // bits 1..3 (A/B): clear those LmAttnArgs::variant bits
   return 0;
 }
+// diagnostic: a bf16-weight, bf16-KV engine runs k_lm_attn<false, 2> where it would run <false, 0> -- the
+// FP8-KV form's data flow and quantiser on a bf16 cache (the appended rows stored dequantised)
+static std::atomic<int> g_lm_attn_kvround{0};
+extern "C" int vv_lm_attn_kvround(int on) {
+  g_lm_attn_kvround = on ? 1 : 0;
+  return 0;
+}
 extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launches record [256][16] phase stamps
   g_lm_attn_stamps = (unsigned long long*)buf;
   return 0;
 }
+// k_lm_attn's KV form for this context: 0 raw rows into a bf16 cache, 1 the FP8 cache (its option), 2 the
+// diagnostic round trip; -1: an FP8 cache without the option (the three launches + k_kv_quant)
+static int lm_attn_kvq(vv_ctx* c) {
+  if (c->kv_dtype) return c->lm_attn_kv8 ? 1 : -1;
+  return g_lm_attn_kvround && c->attn_form == vv_ctx::MLP_BF16 && c->stg.k ? 2 : 0;
+}
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
+  const int kvq = lm_attn_kvq(c);
+  if (kvq < 0) return false;
   // every layer's qkv_w and o_w bound as bf16, or as codes with the context's option on (the W8
   // form: its own residency); a mixed binding, or codes without the option: the three launches
   const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
   if (c->attn_form != vv_ctx::MLP_BF16 && !w8) return false;
-  return g_lm_attn && !c->kv_dtype && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
+  return g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, LA_MAX_KEYS) &&
-         (w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
-             : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)) &&
+         (kvq  ? lm_attn_kvq_fits(w8, kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
+          : w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
+               : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)) &&
          lm_attn_part_floats(P.ntok, P.maxp) * sizeof(float) <= c->la_part.bytes && persist_on(c);
 }
 extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
@@ -1518,7 +1551,9 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
     g.rope.inv_freq = c->lm.inv_freq;
     g.rope.cs_tab = g_rope_tab ? (const bf16*)c->rope_tab.p : nullptr;
     g.rope.kv = c->kv;
-    if (c->kv_dtype) {
+    // (k_lm_attn's KVQ forms stage and quantise inside the launch: the real tables, no prep, no k_kv_quant)
+    const bool one = lm_attn_on(c, P);
+    if (c->kv_dtype && !one) {
       // FP8 KV: the epilogue appends to the staging cache (token m at slot 0, position m; cos / sin
       // from the pass's rows of the real positions), k_kv_quant below moves the rows to the cache
       if (l == 0)
@@ -1529,10 +1564,13 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       g.rope.cs_tab = c->stg_cs;
       g.rope.kv = c->stg;
     }
-    if (lm_attn_on(c, P)) {
+    if (one) {
       LmAttnArgs a;
       memset(&a, 0, sizeof(a));
       a.qkv = g;
+      a.kvq = lm_attn_kvq(c);
+      a.stg = c->stg;
+      a.kv8 = c->kv8;
       a.nw = w.in_norm;
       a.eps = k.rms_eps;
       a.scale = 1.0f / sqrtf((float)d);

@@ -345,9 +345,21 @@ struct LmAttnArgs {
   // exponent per packed row -- bit for bit the bf16 form on the dequantised matrices
   const unsigned char* ow8;     // o_proj codes [H][H]
   const signed char* owe;       // [H]
+  // FP8 KV cache (the KVQ forms, run when kvq != 0; qkv.rope keeps the pass's real slot / position
+  // tables and the real positions' cos / sin): phase 1 appends the rows to the staging cache `stg`
+  // (slot 0, position = the row index), phase 2 runs the rows this pass appends through the e4m3
+  // row quantiser (kv_quant_dev.h) instead of reading them from the cache, and stores them at
+  // their real (slot, position).  kvq = 1: codes + row exponents into kv8 (qkv.rope.kv gives the
+  // strides), the attention reads codes.  kvq = 2 (diagnostic, bf16 weights only): the dequantised
+  // rows into the bf16 cache qkv.rope.kv, the attention reads bf16 -- the bits kvq = 1 computes
+  int kvq, pad2_;
+  KVLayout stg;
+  KV8 kv8;
 };
 bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys);
 bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys);   // the W8 form's own residency
+// the KVQ forms' own residencies: (w8, kvq) = (0, 1), (1, 1), (0, 2)
+bool lm_attn_kvq_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys);
 size_t lm_attn_part_floats(int R, int keys);
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st);
 

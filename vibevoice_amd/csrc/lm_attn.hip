@@ -40,8 +40,29 @@
 // of 6 bf16x8 and converts a fragment to code * 2^e[row] (cvt8s: the bf16 value
 // k_dequant_w8 stores, exactly) where the bf16 form reads the register -- bit for bit the
 // bf16 kernel on the dequantised matrices (tests/test_gpu_w8_lm_attn.py).
+//
+// KVQ (the KV format, beside W8; LmAttnArgs::kvq): 0 = the rows appended raw to a bf16 cache,
+// as above.  1 = the FP8 (e4m3) cache of kv_fp8.hip (KV8: codes in the bf16 geometry + one int8
+// exponent per row; the per-engine option vv_set_lm_attn_kv8): phase 1 writes the K rows and V
+// columns to the context's bf16 staging cache (slot 0, position = the row index; cos / sin of the
+// real position), as the GEMV epilogues do under FP8 KV.  Phase 2 never uses a cache entry this
+// launch writes: a key of a unit that some row m' of the pass appends (the unit's slot, a position
+// inside the unit) is taken from that row's staged K / V rows through the row quantiser
+// (kv_quant_dev.h) -- a pure function, so every unit that holds the key derives the same codes and
+// exponent -- and the one unit whose query row is m' stores them at the real (slot, position).
+// A pass may carry several rows of one slot (a short prompt is one pass below the prefill
+// threshold), so "appended" is decided per key against the pass's tables (kept in LDS), not per
+// tail unit.  The K / V fragments load as codes (8 bytes where bf16 loads 16), convert with
+// cvt8 (exact), and the scales go where k_attn's one-byte form puts them: 2^eK[j] on the fp32
+// score of key j, 2^eV[j] on its fp32 probability before the bf16 rounding, l from the unscaled
+// probabilities.  No k_kv_stage_prep / k_kv_quant launch, no added wait.  2 = diagnostic
+// (vv_lm_attn_kvround): KVQ = 1's data flow and quantiser on a bf16 cache -- the appended rows
+// stored dequantised, the fragments read as bf16 -- the only other producer of the bits KVQ = 1
+// must produce (tests/test_gpu_lm_attn_kv8.py).  Everything is `if constexpr`: <W8, 0> compile to
+// the instruction streams they had before the parameter.
 #include <type_traits>
 
+#include "kv_quant_dev.h"
 #include "persist_dev.h"
 
 namespace la {
@@ -57,17 +78,20 @@ constexpr int RED = XS + XS_B, RED_B = NW * 256 * 4;
 constexpr int PT = RED + RED_B, PT_B = NW * 16 * 32 * 2;
 constexpr int NWS = PT + PT_B, NWS_B = H * 2;              // input_layernorm weight
 constexpr int SM = NWS + NWS_B, SM_B = 64 + 4 * (2 * RMAX + 1) + 12;
+// the KVQ forms' tables: the pass's slots [16], positions [16], and per row the first position this
+// pass appends to the row's slot [16]
+constexpr int KT = SM + SM_B, KT_B = 3 * RMAX * 4;
 // 82 KB: one workgroup per CU (two would share a CU while another idles)
-constexpr int TOTAL = (SM + SM_B) > 82 * 1024 ? (SM + SM_B) : 82 * 1024;
+constexpr int TOTAL = (KT + KT_B) > 82 * 1024 ? (KT + KT_B) : 82 * 1024;
 constexpr int PART = G * D + 2 * G;              // floats per unit partial: O[6][128], then (m, l) x 6
-static_assert(SM + SM_B <= 160 * 1024, "lm attn LDS");
+static_assert(KT + KT_B <= 160 * 1024 && KT % 16 == 0 && TOTAL == 82 * 1024, "lm attn LDS");
 static_assert(GRID == pk::G, "grid waits: 256 arrivals per wait");
 static_assert(KPW * NW == KC && KPW % 2 == 0 && PPW * 2 == KPW, "lm attn W8: a wave's k-blocks are whole pairs");
 }  // namespace la
 
 DEV void la_stamp(const LmAttnArgs& a, int k) { hl_stamp(a.stamps, blockIdx.x, k, 0); }
 
-template <bool W8>
+template <bool W8, int KVQ>
 __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   using namespace la;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -78,6 +102,8 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   float* inv_s = (float*)(smem + SM);   // [16]
   int* pre = (int*)(smem + SM + 64);    // [2R + 1] unit prefix over (row, kv head) pairs
   unsigned* ok_s = (unsigned*)(smem + SM + 64 + 4 * (2 * RMAX + 1));
+  int* tslot = (int*)(smem + KT);       // KVQ: [16] the pass's slots, [16] positions, [16] first appended position
+  int *tpos = tslot + RMAX, *tmin = tpos + RMAX;
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, w = blockIdx.x, R = a.R;
@@ -93,6 +119,13 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   if (threadIdx.x < 2 * RMAX) {
     const int qi = threadIdx.x / NKV;
     nunit = qi < R ? (RP.pos[qi] + 1 + 31) / 32 : 0;
+  }
+  int ts = 0, tp = 0;   // KVQ: row threadIdx.x's slot and position (rows >= R repeat R - 1)
+  if constexpr (KVQ != 0) {
+    if (threadIdx.x < RMAX) {
+      ts = RP.slots[min((int)threadIdx.x, R - 1)];
+      tp = RP.pos[min((int)threadIdx.x, R - 1)];
+    }
   }
   la_stamp(a, 0);
   bf16x4 rv_pre = (bf16x4){0, 0, 0, 0};   // o_proj's residual operand (variant 4: loaded at entry)
@@ -157,10 +190,23 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     }
   }
   if (threadIdx.x < 2 * RMAX) pre[threadIdx.x + 1] = nunit;
+  if constexpr (KVQ != 0) {
+    if (threadIdx.x < RMAX) {
+      tslot[threadIdx.x] = ts;
+      tpos[threadIdx.x] = tp;
+    }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     pre[0] = 0;
     for (int p = 1; p <= 2 * RMAX; ++p) pre[p] += pre[p - 1];
+  }
+  if constexpr (KVQ != 0) {   // (read in phase 2, after the barriers below)
+    if (threadIdx.x < RMAX) {
+      int mn = tp;
+      for (int m2 = 0; m2 < R; ++m2) mn = tslot[m2] == ts ? min(mn, tpos[m2]) : mn;
+      tmin[threadIdx.x] = mn;
+    }
   }
   la_stamp(a, 1);
   if (qt) {
@@ -228,18 +274,27 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
             o1[i] = tobf(rb(v[i] * cs[i]) + rb(-u[i] * sn[i]));
             o2[i] = tobf(rb(u[i] * cs[i]) + rb(v[i] * sn[i]));
           }
-          bf16* dst = hh < NH ? RP.q_out + (long long)m * NH * D + hh * D
+          bf16* dst;
+          if constexpr (KVQ != 0)   // K rows to the staging cache: slot 0, position = the row index
+            dst = hh < NH ? RP.q_out + (long long)m * NH * D + hh * D
+                          : a.stg.k + (long long)(hh - NH) * a.stg.s_head + (long long)m * D;
+          else
+          dst = hh < NH ? RP.q_out + (long long)m * NH * D + hh * D
                               : RP.kv.k + (long long)RP.layer * RP.kv.s_layer + (long long)rs * RP.kv.s_slot +
                                     (long long)(hh - NH) * RP.kv.s_head + (long long)rp * D;
           MemWT::st8(dst + j, o1);
           MemWT::st8(dst + j + 64, o2);
         }
       } else if (m < R) {   // V cache in 32-position blocks of [dim][position] (common.h v_off)
-        bf16* hb = RP.kv.v + (long long)RP.layer * RP.kv.s_layer + (long long)rs * RP.kv.s_slot +
+        bf16* hb;
+        if constexpr (KVQ != 0) hb = a.stg.v + (long long)(hh - NH - NKV) * a.stg.s_head;
+        else
+        hb = RP.kv.v + (long long)RP.layer * RP.kv.s_layer + (long long)rs * RP.kv.s_slot +
                    (long long)(hh - NH - NKV) * RP.kv.s_head;
         const int dim0 = (n0 % D) + 4 * g4;
+        const int vp = KVQ != 0 ? m : rp;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) MemWT::st2(hb + v_off(dim0 + i, rp), tobf(v[i]));
+        for (int i = 0; i < 4; ++i) MemWT::st2(hb + v_off(dim0 + i, vp), tobf(v[i]));
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -277,6 +332,27 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     const bf16* qrow = RP.q_out + (long long)qi * NH * D + (kh * G + min(r16, G - 1)) * D + 8 * g4;
 #pragma unroll
     for (int c = 0; c < 4; ++c) qf[c] = MemWT::ld16(qrow + 32 * c);
+    // KVQ = 1: the fragments as e4m3 codes (8 bytes where bf16 loads 16) and the row exponents of this
+    // lane's score columns, keys c0 + 16 tt + r (clamped like the keys: masked columns read a valid row's)
+    u32x2 kq[2][4], vq[8];
+    int xk[2] = {0, 0}, xv[2] = {0, 0};
+    if constexpr (KVQ == 1) {
+      const unsigned char* K8 = a.kv8.k + cbase;
+      const unsigned char* V8 = a.kv8.v + cbase;
+      const signed char* EK = a.kv8.ek + cbase / D;
+      const signed char* EV = a.kv8.ev + cbase / D;
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        const int key = min(c0 + 16 * tt + r16, w1 - 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) kq[tt][c] = hl_ldnt8h(K8 + (long long)key * D + 32 * c + 8 * g4);
+        xk[tt] = EK[key];
+        xv[tt] = EV[key];
+      }
+      const int kb = min(c0 + 8 * g4, (w1 - 1) & ~7);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vq[j] = hl_ldnt8h(V8 + v_off(16 * j + r16, kb));
+    } else {
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
       const int key = min(c0 + 16 * tt + r16, w1 - 1);
@@ -286,6 +362,129 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     const int kb = min(c0 + 8 * g4, (w1 - 1) & ~7);
 #pragma unroll
     for (int j = 0; j < 8; ++j) vf[j] = hl_ldnt(VB + v_off(16 * j + r16, kb));
+    }
+    if constexpr (KVQ != 0) {
+      // The keys this pass appends (row m2 of the pass: the unit's slot, a position in [c0, w1)) are not
+      // in the cache: what the loads above returned at their positions is replaced here and never used.
+      // Every unit that holds such a key takes row m2's staged K row and V row (written through by phase
+      // 1's workgroups before wait 1; nt loads bypass L1), runs them through the row quantiser -- a pure
+      // function, so every reader derives the same values -- and uses code * 2^e (KVQ = 1: the codes and
+      // the exponent).  The unit of query row m2 itself also stores the result at the real (slot,
+      // position); nothing reads that entry in this launch.  All lanes load the row: K in the fragment
+      // layout (dims 32 c + 8 g ..), V as dims 16 j + r; a row's amax is then the wave's.
+      if (w1 > __builtin_amdgcn_readfirstlane(tmin[qi])) {
+        const int uslot = __builtin_amdgcn_readfirstlane(tslot[qi]);
+        for (int m2 = 0; m2 < R; ++m2) {
+          const int ps = __builtin_amdgcn_readfirstlane(tpos[m2]);
+          if (__builtin_amdgcn_readfirstlane(tslot[m2]) != uslot || ps < c0 || ps >= w1) continue;
+          const bf16* SK = a.stg.k + (long long)kh * a.stg.s_head + (long long)m2 * D;
+          const bf16* SV = a.stg.v + (long long)kh * a.stg.s_head;
+          bf16x8 sk[4];
+          bf16 sv[8];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) sk[c] = hl_ldnt(SK + 32 * c + 8 * g4);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            sv[j] = __builtin_bit_cast(bf16, __builtin_nontemporal_load((const gu16*)(SV + v_off(16 * j + r16, m2))));
+          float ak = 0.f, av = 0.f;
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ak = fmaxf(ak, fabsf(bf(sk[c][i])));
+#pragma unroll
+          for (int j = 0; j < 8; ++j) av = fmaxf(av, fabsf(bf(sv[j])));
+          const int eK = row_exp(wave_max(ak)), eV = row_exp(wave_max(av));
+          u32x2 pk[4];      // K codes, fragment order
+          unsigned cv[8];   // V codes of dims 16 j + r
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            unsigned cc[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) cc[i] = enc_e4m3(ldexpf(bf(sk[c][i]), -eK));
+            pk[c][0] = cc[0] | (cc[1] << 8) | (cc[2] << 16) | (cc[3] << 24);
+            pk[c][1] = cc[4] | (cc[5] << 8) | (cc[6] << 16) | (cc[7] << 24);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) cv[j] = enc_e4m3(ldexpf(bf(sv[j]), -eV));
+          const int ee = ps - (c0 + 8 * g4);   // this lane's V fragments hold key ps at element ee (0 .. 7)
+          const bool own = m2 == qi;
+          if constexpr (KVQ == 1) {
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+              const bool hit = c0 + 16 * tt + r16 == ps;
+#pragma unroll
+              for (int c = 0; c < 4; ++c) {
+                kq[tt][c][0] = hit ? pk[c][0] : kq[tt][c][0];
+                kq[tt][c][1] = hit ? pk[c][1] : kq[tt][c][1];
+              }
+              xk[tt] = hit ? eK : xk[tt];
+              xv[tt] = hit ? eV : xv[tt];
+            }
+            const unsigned sh = 8u * (unsigned)(ee & 3);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const unsigned lo = (vq[j][0] & ~(0xffu << sh)) | (cv[j] << sh);
+              const unsigned hi = (vq[j][1] & ~(0xffu << sh)) | (cv[j] << sh);
+              vq[j][0] = (ee >= 0 && ee < 4) ? lo : vq[j][0];
+              vq[j][1] = (ee >= 4 && ee < 8) ? hi : vq[j][1];
+            }
+            if (own) {
+              if (r16 == 0) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) *(u32x2*)(a.kv8.k + cbase + (long long)ps * D + 32 * c + 8 * g4) = pk[c];
+              }
+              if (g4 == 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a.kv8.v[cbase + v_off(16 * j + r16, ps)] = (unsigned char)cv[j];
+              }
+              if (lane == 0) {
+                a.kv8.ek[cbase / D + ps] = (signed char)eK;
+                a.kv8.ev[cbase / D + ps] = (signed char)eV;
+              }
+            }
+          } else {   // KVQ = 2: the dequantised rows (k_kv_rows' read expression), bf16 throughout
+            bf16x8 dk[4];
+            bf16 dv[8];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+              for (int i = 0; i < 8; ++i) dk[c][i] = tobf(ldexpf(dec_e4m3((pk[c][i >> 2] >> (8 * (i & 3))) & 0xffu), eK));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dv[j] = tobf(ldexpf(dec_e4m3(cv[j]), eV));
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+              const bool hit = c0 + 16 * tt + r16 == ps;
+#pragma unroll
+              for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) kf[tt][c][i] = hit ? dk[c][i] : kf[tt][c][i];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) vf[j][e] = ee == e ? dv[j] : vf[j][e];
+            if (own) {
+              if (r16 == 0) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) *(bf16x8*)(RP.kv.k + cbase + (long long)ps * D + 32 * c + 8 * g4) = dk[c];
+              }
+              if (g4 == 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) RP.kv.v[cbase + v_off(16 * j + r16, ps)] = dv[j];
+              }
+            }
+          }
+        }
+      }
+      if constexpr (KVQ == 1) {   // codes -> bf16 (exact), then the bf16 step
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) kf[tt][c] = cvt8(kq[tt][c][0], kq[tt][c][1]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vf[j] = cvt8(vq[j][0], vq[j][1]);
+      }
+    }
     if (r16 >= G) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) qf[c] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
@@ -307,6 +506,10 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     float mv[4], lv[4], pp[2][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      if constexpr (KVQ == 1) {   // k_attn's one-byte form: the key's 2^eK on the fp32 score
+        sacc[0][i] = ldexpf(sacc[0][i], xk[0]);
+        sacc[1][i] = ldexpf(sacc[1][i], xk[1]);
+      }
       const float s0 = c0 + r16 < w1 ? sacc[0][i] * a.scale : -INFINITY;
       const float s1 = c0 + 16 + r16 < w1 ? sacc[1][i] * a.scale : -INFINITY;
       const float mx = row16_max(fmaxf(s0, s1));
@@ -319,7 +522,12 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)pp[tt][i];
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (KVQ == 1)   // ... and the key's 2^eV on the fp32 probability before its rounding (l: unscaled)
+          ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)ldexpf(pp[tt][i], xv[tt]);
+        else
+        ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)pp[tt][i];
+      }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const bf16x8 pa = *(const bf16x8*)(ptw + r16 * 32 + 8 * g4);
     f32x4 o[8];
@@ -450,31 +658,63 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   la_stamp(a, 8);
 }
 
+static bool la_shape_ok(int H, int nh, int nkv, int d, int R, int keys) {
+  return H == la::H && nh == la::NH && nkv == la::NKV && d == la::D && R >= 1 && R <= la::RMAX && keys >= 1 &&
+         keys <= LA_MAX_KEYS;
+}
 bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys) {
-  if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D || R < 1 || R > la::RMAX || keys < 1 ||
-      keys > LA_MAX_KEYS)
-    return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false>, la::NT, la::TOTAL, la::GRID);
+  if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false, 0>, la::NT, la::TOTAL, la::GRID);
   return ok;
 }
 bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys) {
-  if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D || R < 1 || R > la::RMAX || keys < 1 ||
-      keys > LA_MAX_KEYS)
-    return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<true>, la::NT, la::TOTAL, la::GRID);
+  if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<true, 0>, la::NT, la::TOTAL, la::GRID);
   return ok;
+}
+bool lm_attn_kvq_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys) {
+  if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  if (kvq == 1 && !w8) {
+    static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false, 1>, la::NT, la::TOTAL, la::GRID);
+    return ok;
+  }
+  if (kvq == 1) {
+    static const bool ok = persist_resident_kernel((const void*)k_lm_attn<true, 1>, la::NT, la::TOTAL, la::GRID);
+    return ok;
+  }
+  if (kvq == 2 && !w8) {
+    static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false, 2>, la::NT, la::TOTAL, la::GRID);
+    return ok;
+  }
+  return false;
 }
 
 size_t lm_attn_part_floats(int R, int keys) { return (size_t)R * la::NKV * ((keys + 31) / 32) * la::PART; }
 
-// the W8 form when a code pointer is set (all four of q|k|v's and o_proj's codes and exponents, or it is an error)
+// the W8 form when a code pointer is set (all four of q|k|v's and o_proj's codes and exponents, or it is an
+// error); the KV form from a.kvq (1: the FP8 cache a.kv8; 2: the diagnostic round trip, bf16 weights only),
+// which needs the staging cache and, for the bounds of phase 1's staged append, its 16 positions
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st) {
   const bool w8 = a.qkv.w8 || a.qkv.w8e || a.ow8 || a.owe;
   if (w8 && (!a.qkv.w8 || !a.qkv.w8e || !a.ow8 || !a.owe)) return 1;
-  if (!(w8 ? lm_attn_w8_fits(la::H, la::NH, la::NKV, la::D, a.R, keys) : lm_attn_fits(la::H, la::NH, la::NKV, la::D, a.R, keys)) ||
-      a.qkv.M != a.R || a.qkv.N != la::NQKV || a.qkv.K != la::H || !a.qkv.epi.bias || !a.part || !a.att || !a.sync || !a.err)
+  const int kvq = a.kvq;
+  if (kvq < 0 || kvq > 2 || (kvq == 2 && w8)) return 1;
+  if (kvq && (!a.stg.k || !a.stg.v || a.stg.max_ctx < la::RMAX || a.stg.s_head < (long long)la::D * 32)) return 1;
+  if (kvq == 1 && (!a.kv8.k || !a.kv8.v || !a.kv8.ek || !a.kv8.ev || a.qkv.rope.kv.s_layer % la::D ||
+                   a.qkv.rope.kv.s_slot % la::D || a.qkv.rope.kv.s_head % la::D))
+    return 1;
+  if (kvq == 2 && (!a.qkv.rope.kv.k || !a.qkv.rope.kv.v)) return 1;
+  const bool fits = kvq  ? lm_attn_kvq_fits(w8, kvq, la::H, la::NH, la::NKV, la::D, a.R, keys)
+                    : w8 ? lm_attn_w8_fits(la::H, la::NH, la::NKV, la::D, a.R, keys)
+                         : lm_attn_fits(la::H, la::NH, la::NKV, la::D, a.R, keys);
+  if (!fits || a.qkv.M != a.R || a.qkv.N != la::NQKV || a.qkv.K != la::H || !a.qkv.epi.bias || !a.part || !a.att ||
+      !a.sync || !a.err)
     return 3;
-  if (w8) hipLaunchKernelGGL(k_lm_attn<true>, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
-  else hipLaunchKernelGGL(k_lm_attn<false>, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
+  const dim3 grid(la::GRID), blk(la::NT);
+  if (kvq == 1 && w8) hipLaunchKernelGGL((k_lm_attn<true, 1>), grid, blk, la::TOTAL, st, a);
+  else if (kvq == 1) hipLaunchKernelGGL((k_lm_attn<false, 1>), grid, blk, la::TOTAL, st, a);
+  else if (kvq == 2) hipLaunchKernelGGL((k_lm_attn<false, 2>), grid, blk, la::TOTAL, st, a);
+  else if (w8) hipLaunchKernelGGL((k_lm_attn<true, 0>), grid, blk, la::TOTAL, st, a);
+  else hipLaunchKernelGGL((k_lm_attn<false, 0>), grid, blk, la::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
+from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
                       pack)
 
 _VALID_IDS_DEFAULT = None
@@ -77,7 +77,7 @@ class Engine:
 
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
-                 persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False):
+                 persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -98,13 +98,17 @@ class Engine:
         codes + a power-of-two scale per cached row (vv_set_kv_dtype; tp_size 1 only).
         lm_attn_w8: True runs the one-launch LM attention kernel on the FP8 codes
         (vv_set_lm_attn_w8; default off: an FP8 engine runs the q|k|v, attention and
-        o_proj launches).  Needs FP8 weights, a bf16 KV cache and tp_size 1."""
+        o_proj launches).  Needs FP8 weights, tp_size 1 and a bf16 KV cache (or lm_attn_kv8).
+        lm_attn_kv8: True runs the one-launch LM attention kernel on the FP8 KV cache
+        (vv_set_lm_attn_kv8; default off: an FP8-KV engine runs the q|k|v, quantise,
+        attention and o_proj launches).  Needs kv_dtype="fp8_e4m3" and tp_size 1."""
         persistent = normalize_persistent(persistent)
         check_weight_dtype(weight_dtype, tp_size)
         check_kv_dtype(kv_dtype, tp_size)
+        self.lm_attn_kv8 = check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
         packed_fp8 = packed is not None and any(k.endswith("_w" + W8_CODES) for k in packed)
         self.lm_attn_w8 = check_lm_attn_w8(lm_attn_w8, weight_dtype if packed is None else "fp8_e4m3" if packed_fp8 else None,
-                                           kv_dtype, tp_size)
+                                           kv_dtype, tp_size, lm_attn_kv8=self.lm_attn_kv8)
         self.kv_dtype = kv_dtype
         L = _lib.lib()
         self.cfg = cfg
@@ -143,6 +147,8 @@ class Engine:
                 _lib.check(L.vv_set_kv_dtype(h, 1), "set_kv_dtype")
             if self.lm_attn_w8:
                 _lib.check(L.vv_set_lm_attn_w8(h, 1), "set_lm_attn_w8")
+            if self.lm_attn_kv8:
+                _lib.check(L.vv_set_lm_attn_kv8(h, 1), "set_lm_attn_kv8")
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")

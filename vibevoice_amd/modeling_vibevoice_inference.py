@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .engine import Engine
-from .weights import check_kv_dtype, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
+from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
 
 
 @dataclass
@@ -174,7 +174,7 @@ class VibeVoiceTokenConstraintProcessor:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VibeVoiceConfig, state_dict, device="cuda", attn_implementation="hip",
                  max_batch=8, max_ctx=8192, tp_group=None, tp_head=None, persistent=True, weight_dtype=None,
-                 kv_dtype=None, lm_attn_w8=False):
+                 kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False):
         """tp_group: a torch.distributed process group whose ranks (one per GPU)
         tensor-parallel-shard the Qwen2 backbone over RCCL; every
         rank then runs generate() on the same inputs (SPMD) and gets the same
@@ -192,14 +192,19 @@ class VibeVoiceForConditionalGenerationInference:
         the cache's bytes (INTEGRATION.md §2 "Capacity / KV formats"); the same
         rules as weight_dtype.
         lm_attn_w8: True runs the one-launch LM attention kernel on the FP8 codes
-        (default off; needs weight_dtype="fp8_e4m3", a bf16 KV cache and no
-        tensor-parallel group, else ValueError; INTEGRATION.md §2 "Weight formats")."""
+        (default off; needs weight_dtype="fp8_e4m3", a bf16 KV cache or lm_attn_kv8,
+        and no tensor-parallel group, else ValueError; INTEGRATION.md §2 "Weight formats").
+        lm_attn_kv8: True runs the one-launch LM attention kernel on the FP8 KV cache
+        (default off; needs kv_dtype="fp8_e4m3" and no tensor-parallel group, else
+        ValueError; INTEGRATION.md §2 "Capacity / KV formats")."""
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
-        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype)
+        check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
+        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
         self.weight_dtype = weight_dtype
         self.kv_dtype = kv_dtype
         self.lm_attn_w8 = bool(lm_attn_w8)
+        self.lm_attn_kv8 = lm_attn_kv8
         self.config = config
         self.attn_implementation = attn_implementation
         self.device = torch.device(device)
@@ -211,7 +216,8 @@ class VibeVoiceForConditionalGenerationInference:
             tp_rank, tp_size = dist.get_rank(tp_group), dist.get_world_size(tp_group)
             check_weight_dtype(weight_dtype, tp_size)
             check_kv_dtype(kv_dtype, tp_size)
-            check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size)
+            check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
+            check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size, lm_attn_kv8=lm_attn_kv8)
             if tp_size > 1:
                 box = [Engine.tp_unique_id() if tp_rank == 0 else None]
                 dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
@@ -223,7 +229,8 @@ class VibeVoiceForConditionalGenerationInference:
                              tp_rank=tp_rank, tp_size=tp_size, tp_unique_id=uid, persistent=persistent,
                              **({} if weight_dtype is None else {"weight_dtype": weight_dtype}),
                              **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
-                             **({"lm_attn_w8": True} if lm_attn_w8 else {}))
+                             **({"lm_attn_w8": True} if lm_attn_w8 else {}),
+                             **({"lm_attn_kv8": True} if lm_attn_kv8 else {}))
         self.ddpm_inference_steps = config.diffusion_head_config.ddpm_num_inference_steps
         self.model = _ModelView(self)
         self.use_graphs = True          # capture the steady-state loop body into hipGraphs
@@ -271,7 +278,8 @@ class VibeVoiceForConditionalGenerationInference:
 
     @classmethod
     def from_pretrained(cls, path, torch_dtype=torch.bfloat16, device_map="cuda", attn_implementation="hip",
-                        synthetic_seed=0, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, **kw):
+                        synthetic_seed=0, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False,
+                        **kw):
         """`path`: a checkpoint dir (config.json + *.safetensors), or
         "synthetic:1.5B" / "synthetic:Large" for seeded random weights at the
         real shapes (no checkpoints are reachable offline).
@@ -284,10 +292,12 @@ class VibeVoiceForConditionalGenerationInference:
         `weight_dtype`: None (bf16) or "fp8_e4m3": the LM projections are
         quantised from the bf16 checkpoint while loading (no FP8 on-disk format).
         `kv_dtype`: None (bf16) or "fp8_e4m3": the LM's KV cache format.
-        `lm_attn_w8`: True runs the one-launch LM attention kernel on FP8 weights."""
+        `lm_attn_w8`: True runs the one-launch LM attention kernel on FP8 weights.
+        `lm_attn_kv8`: True runs the one-launch LM attention kernel on the FP8 KV cache."""
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
-        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype)
+        check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
+        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
         resolve_dtype(torch_dtype)
         dev = resolve_device(device_map)
         if str(path).startswith("synthetic:"):
@@ -297,7 +307,7 @@ class VibeVoiceForConditionalGenerationInference:
             cfg = VibeVoiceConfig.from_json_file(os.path.join(path, "config.json"))
             sd = load_state_dict(path, cfg)
         return cls(cfg, sd, dev, attn_implementation=attn_implementation, weight_dtype=weight_dtype,
-                   kv_dtype=kv_dtype, lm_attn_w8=lm_attn_w8, **kw)
+                   kv_dtype=kv_dtype, lm_attn_w8=lm_attn_w8, lm_attn_kv8=lm_attn_kv8, **kw)
 
     @classmethod
     def _from_config(cls, config, torch_dtype=None, device_map="cuda", attn_implementation="hip", seed=0,

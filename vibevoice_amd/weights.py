@@ -232,19 +232,34 @@ def check_kv_dtype(kv_dtype, tp_size=1):
     return kv_dtype
 
 
-def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1):
+def check_lm_attn_kv8(lm_attn_kv8, kv_dtype=None, tp_size=1):
+    """The per-engine option that runs the one-launch LM attention kernel on an
+    FP8 KV cache (vv_set_lm_attn_kv8): it needs kv_dtype="fp8_e4m3" and tp_size 1."""
+    if not isinstance(lm_attn_kv8, bool):
+        raise ValueError(f"lm_attn_kv8={lm_attn_kv8!r}: expected True or False")
+    if lm_attn_kv8:
+        if kv_dtype != "fp8_e4m3":
+            raise ValueError("lm_attn_kv8=True needs an FP8 KV cache (kv_dtype='fp8_e4m3'); "
+                             f"this engine's kv_dtype is {kv_dtype!r} (bf16)")
+        if tp_size > 1:
+            raise ValueError(f"lm_attn_kv8=True is not supported with tensor parallelism (tp_size={tp_size})")
+    return lm_attn_kv8
+
+
+def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1, *, lm_attn_kv8=False):
     """The per-engine option that runs the one-launch LM attention kernel on FP8
     weights (vv_set_lm_attn_w8): it needs FP8 weights (`weight_dtype` is the
-    format the weights are, or were, packed in), a bf16 KV cache and tp_size 1."""
+    format the weights are, or were, packed in), tp_size 1, and a bf16 KV cache --
+    or an FP8 one whose own option `lm_attn_kv8` is on (check_lm_attn_kv8)."""
     if lm_attn_w8 not in (False, True, 0, 1):
         raise ValueError(f"lm_attn_w8={lm_attn_w8!r}: expected True or False")
     if lm_attn_w8:
         if weight_dtype != "fp8_e4m3":
             raise ValueError("lm_attn_w8=True needs FP8 weights (weight_dtype='fp8_e4m3'); "
                              f"this engine's are {weight_dtype or 'bf16'}")
-        if kv_dtype is not None:
+        if kv_dtype is not None and lm_attn_kv8 is not True:
             raise ValueError(f"lm_attn_w8=True is not supported with kv_dtype={kv_dtype!r}: "
-                             "the one-launch attention kernel reads a bf16 KV cache")
+                             "the one-launch attention kernel reads a bf16 KV cache unless lm_attn_kv8=True")
         if tp_size > 1:
             raise ValueError(f"lm_attn_w8=True is not supported with tensor parallelism (tp_size={tp_size})")
     return bool(lm_attn_w8)
