@@ -117,7 +117,8 @@ int vv_kv_bytes(vv_ctx* ctx, long long* bytes);
  * k_lm_attn's W8 form (csrc/lm_attn.hip: the q|k|v and o_proj tiles read as e4m3
  * codes + row exponents, bit for bit the bf16 kernel on the dequantised
  * matrices) where every layer's qkv_w and o_w are bound as FP8 pairs and the
- * kernel's other conditions hold (<= 16 decode rows, <= 4,096 keys, a bf16 KV
+ * kernel's other conditions hold (<= 16 decode rows, <= 4,096 keys or
+ * vv_set_lm_attn_max_keys, a bf16 KV
  * cache or vv_set_lm_attn_kv8, no tensor parallelism); on = 0 (the default) keeps an FP8 engine on the
  * q|k|v, attention and o_proj launches.  A context whose qkv_w / o_w are all
  * bf16 runs the bf16 form whatever the option; a mix of the two runs the three
@@ -140,6 +141,21 @@ int vv_lm_attn_w8(vv_ctx* ctx);
  *   vv_lm_attn_kv8: the context's option (0 / 1) */
 int vv_set_lm_attn_kv8(vv_ctx* ctx, int on);
 int vv_lm_attn_kv8(vv_ctx* ctx);
+
+/* The longest decode pass, in keys, that runs the one-launch LM attention kernel.
+ * The default, 4,096, is the kernel's short form (an attention unit = 32 keys);
+ * a pass planned past it -- a captured graph is planned at max_ctx -- runs the
+ * q|k|v, attention and o_proj launches.  A larger value (4,096 .. the engine's
+ * max_ctx) lets such passes run the kernel's long form: a unit covers 32 s keys,
+ * s = ceil(row length / 4,096) decided per row inside the kernel, so rows of at
+ * most 4,096 keys compute the short form's bits.  bf16 and FP8 weights
+ * (vv_set_lm_attn_w8); a bf16 KV cache -- an FP8-KV context keeps its own
+ * launches past 4,096 keys whatever the value.  Callable after
+ * vv_create and before vv_finalize; later calls, values outside the range and
+ * tensor-parallel engines are errors.
+ *   vv_lm_attn_max_keys: the context's option */
+int vv_set_lm_attn_max_keys(vv_ctx* ctx, int keys);
+int vv_lm_attn_max_keys(vv_ctx* ctx);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

@@ -223,7 +223,8 @@ int vv_lm_ffn_stamps(void* buf);
 int vv_head_fin(int on);
 int vv_head_fin_active(vv_ctx* ctx, int n);
 /* Diagnostic switch: the LM attention half at decode (input_layernorm .. o_proj
- * + residual, <= 16 rows, contexts <= 4,096 keys) as one launch (lm_attn.hip;
+ * + residual, <= 16 rows, contexts <= 4,096 keys or the context's
+ * vv_set_lm_attn_max_keys) as one launch (lm_attn.hip;
  * 1, default) or the q|k|v, attention and o_proj launches (0); whether it applies
  * to this context at ntok rows over max_pos_p1 keys; and per-workgroup phase
  * stamps of its launches ([256][16] u64, overwritten per launch; NULL = off). */
@@ -236,6 +237,11 @@ int vv_lm_attn_stamps(void* buf);
  * cache and read as bf16) where it would run the plain form (1), or the plain
  * form (0, default) -- the bits the FP8-KV form must produce. */
 int vv_lm_attn_kvround(int on);
+/* Diagnostic: the one-launch kernel's attention units for a row of `len` keys
+ * (1 .. 2^20): out[0] = steps of 32 keys per unit (1 while len <= 4,096),
+ * out[1] = units per (row, kv head) (<= 128); the function the kernel itself
+ * evaluates per row (kernels.h la_unit_steps / la_unit_count). */
+int vv_diag_lm_attn_plan(int len, int* out);
 /* Diagnostic (bench.py): `reps` passes over the LM layers' attention halves alone
  * on ntok decode rows (embeds [ntok][H] as layer 0's input, slots / positions as
  * for vv_lm_forward). */

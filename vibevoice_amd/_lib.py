@@ -44,6 +44,8 @@ EXPORTS = [
     ("vv_lm_attn_w8", I, [P]),
     ("vv_set_lm_attn_kv8", I, [P, I]),
     ("vv_lm_attn_kv8", I, [P]),
+    ("vv_set_lm_attn_max_keys", I, [P, I]),
+    ("vv_lm_attn_max_keys", I, [P]),
     ("vv_set_schedule", I, [P, I, ctypes.POINTER(F), P, P]),
     ("vv_lm_forward", I, [P, I, P, I, P, P, I, I, P, P, P, P]),
     ("vv_kv_copy", I, [P, I, P, P, P, P]),
@@ -104,6 +106,7 @@ EXPORTS = [
     ("vv_lm_attn", I, [I]),
     ("vv_lm_attn_kvround", I, [I]),
     ("vv_lm_attn_active", I, [P, I, I]),
+    ("vv_diag_lm_attn_plan", I, [I, ctypes.POINTER(I)]),
     ("vv_lm_attn_stamps", I, [P]),
     ("vv_lm_attn_replay", I, [P, I, P, P, P, I, I, P]),
     ("vv_lm_mlp_replay", I, [P, I, P, P, I, P]),

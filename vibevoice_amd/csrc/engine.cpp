@@ -251,6 +251,9 @@ struct vv_ctx {
   // context's option too (vv_set_lm_attn_kv8 before vv_finalize, default off: an FP8-KV engine
   // runs q|k|v, k_kv_quant, k_attn, o_proj)
   int lm_attn_kv8 = 0;
+  // the longest pass (keys) the one-launch attention kernel is planned for (vv_set_lm_attn_max_keys before
+  // vv_finalize; default LA_MAX_KEYS: the short form only, three launches past it)
+  int lm_attn_max_keys = LA_MAX_KEYS;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
   // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
   // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
@@ -1056,6 +1059,18 @@ int vv_set_lm_attn_kv8(vv_ctx* c, int on) {
   return 0;
 }
 int vv_lm_attn_kv8(vv_ctx* c) { return c ? c->lm_attn_kv8 : 0; }
+int vv_set_lm_attn_max_keys(vv_ctx* c, int keys) {
+  if (!c) FAIL("vv_set_lm_attn_max_keys: null context");
+  if (c->finalized) FAIL("vv_set_lm_attn_max_keys after vv_finalize: the attention half's kernels are already chosen");
+  if (c->tp_size > 1 || c->comm) FAIL("vv_set_lm_attn_max_keys is not supported on a tensor-parallel engine");
+  const int hi = std::min(c->cfg.max_ctx, LA_LONG_MAX_KEYS);
+  if (keys < LA_MAX_KEYS || keys > hi)
+    FAIL("vv_set_lm_attn_max_keys: " + std::to_string(keys) + " is outside [" + std::to_string(LA_MAX_KEYS) + ", " +
+         std::to_string(hi) + "] (4,096 .. the engine's max_ctx)");
+  c->lm_attn_max_keys = keys;
+  return 0;
+}
+int vv_lm_attn_max_keys(vv_ctx* c) { return c ? c->lm_attn_max_keys : 0; }
 int vv_kv_bytes(vv_ctx* c, long long* bytes) {
   if (!c || !bytes) FAIL("vv_kv_bytes: null argument");
   if (!c->finalized) FAIL("vv_kv_bytes before vv_finalize: the KV cache is not allocated yet");
@@ -1170,15 +1185,22 @@ int vv_finalize(vv_ctx* c) {
   const bool lf16_fits =
       mlp_one && (mlp_w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, 16) : lm_ffn16_fits(k.hidden, k.intermediate, 16));
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
-  const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, LA_MAX_KEYS);
+  const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, c->lm_attn_max_keys);
   // (the W8 form's own residency where this context will run it: codes throughout + its option)
   // (... and the FP8-KV form's where an FP8-KV context's option selects it)
   const bool la_w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
   const bool la_kv8 = c->kv_dtype && c->lm_attn_kv8;
-  const bool la_fits = (la_kv8  ? lm_attn_kvq_fits(la_w8, 1, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
-                        : la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
-                                : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)) &&
+  // (the short form's residency, and with lm_attn_max_keys past LA_MAX_KEYS the long form's as well, both
+  // queried here: an engine with the option runs the short form for passes planned at <= LA_MAX_KEYS.  The
+  // long form reads a bf16 cache: an FP8-KV engine keeps k_kv_quant + k_attn past LA_MAX_KEYS.)
+  const int la_short = std::min(la_keys, LA_MAX_KEYS);
+  const bool la_fits = (la_kv8  ? lm_attn_kvq_fits(la_w8, 1, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)
+                        : la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)
+                                : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
+  if (la_fits && la_keys > LA_MAX_KEYS && !la_kv8)
+    (void)(la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
+                 : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys));
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
   HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
@@ -1481,7 +1503,7 @@ static void tp_residual(vv_ctx* c, GemmArgs& g, const RowMap& res) {
 }
 
 // the LM attention half at decode in one launch (lm_attn.hip): <= 16 rows of the
-// 1.5B shapes, contexts <= LA_MAX_KEYS, unsharded, while the context is the
+// 1.5B shapes, contexts <= the context's lm_attn_max_keys (default LA_MAX_KEYS), unsharded, while the context is the
 // device's only registered one; 0 = the three launches (q|k|v, k_attn, o_proj)
 static std::atomic<int> g_lm_attn{1};
 static std::atomic<unsigned long long*> g_lm_attn_stamps{nullptr};
@@ -1516,7 +1538,7 @@ static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   if (c->attn_form != vv_ctx::MLP_BF16 && !w8) return false;
   return g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
-         P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, LA_MAX_KEYS) &&
+         P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, c->lm_attn_max_keys) &&
          (kvq  ? lm_attn_kvq_fits(w8, kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
           : w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
                : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)) &&

@@ -321,8 +321,18 @@ int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 
 // ---- the LM attention half at decode in one launch (lm_attn.hip): input_layernorm
 // -> q|k|v + RoPE + KV append -> attention -> o_proj + residual, R <= 16 rows of
-// the 1.5B shapes, contexts <= LA_MAX_KEYS keys
+// the 1.5B shapes.  Contexts <= LA_MAX_KEYS keys: the short form, an attention unit = 32 keys of one
+// (row, kv head).  A pass planned past that (up to LA_LONG_MAX_KEYS; the per-engine option
+// vv_set_lm_attn_max_keys) runs the long form: a unit = s steps of 32 keys, s from the row's own length
+// in the kernel, so a row holds at most LA_MAX_KEYS / 32 = 128 units at any length and the merge
+// phase and the partials' workspace are the short form's.
 constexpr int LA_MAX_KEYS = 4096;
+constexpr int LA_LONG_MAX_KEYS = 1 << 20;
+// steps per unit of a row of `len` keys (1 while len <= LA_MAX_KEYS: the short form's units), and its units
+__host__ __device__ constexpr int la_unit_steps(int len) { return len <= LA_MAX_KEYS ? 1 : (len + LA_MAX_KEYS - 1) / LA_MAX_KEYS; }
+__host__ __device__ constexpr int la_unit_count(int len) { return (len + 32 * la_unit_steps(len) - 1) / (32 * la_unit_steps(len)); }
+static_assert(la_unit_count(LA_MAX_KEYS) == 128 && la_unit_count(LA_MAX_KEYS + 1) == 65 && la_unit_count(LA_LONG_MAX_KEYS) == 128,
+              "k_lm_attn: at most 128 units per (row, kv head) -- the merge wave's two (m, l) per lane");
 struct LmAttnArgs {
   GemmArgs qkv;      // the q|k|v projection as launch_gemm would run it: M = R, a = the A rows,
                      // w = qkv_w, epi = EPI_ROPE (+ bias), rope = q_out / KV cache / pos / slots

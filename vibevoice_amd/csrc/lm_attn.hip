@@ -1,7 +1,8 @@
 // The LM attention half at decode in ONE launch (k_lm_attn): input_layernorm ->
 // q|k|v projection (+bias) -> RoPE -> KV append -> GQA attention over the
 // compacted per-row cache -> o_proj -> residual, for R <= 16 query rows of the
-// 1.5B shapes (H 1,536, 12 q / 2 kv heads of 128) at contexts <= LA_MAX_KEYS.
+// 1.5B shapes (H 1,536, 12 q / 2 kv heads of 128) at contexts <= LA_MAX_KEYS (LONG
+// below: past that).
 // Reference: transformers Qwen2Attention (modeling_qwen2.py:99-134, 150-173,
 // 195-247) as VibeVoiceModel.forward calls it per layer
 // (vibevoice/modular/modeling_vibevoice.py:169-209) inside the generate loop
@@ -60,6 +61,14 @@
 // stored dequantised, the fragments read as bf16 -- the only other producer of the bits KVQ = 1
 // must produce (tests/test_gpu_lm_attn_kv8.py).  Everything is `if constexpr`: <W8, 0> compile to
 // the instruction streams they had before the parameter.
+//
+// LONG (the third parameter, bf16 KV only; a pass planned past LA_MAX_KEYS keys, which an engine allows
+// with vv_set_lm_attn_max_keys): phase 2 is la_long_units -- a unit covers 32 s keys, s =
+// la_unit_steps(len) = ceil(len / 4,096) per row, computed in the kernel from the pass's position table,
+// so a captured graph replays as rows grow across the s edges.  One partial per unit, at most 128 units
+// per (row, kv head): phases 1, 3 and 4, the waits, the stamps and the partials' workspace are the short
+// form's, and rows of <= 4,096 keys (s = 1) get the short form's units, order and bits.  The short
+// instantiations' bodies are untouched: they compile to the instruction streams they had before.
 #include <type_traits>
 
 #include "kv_quant_dev.h"
@@ -91,9 +100,145 @@ static_assert(KPW * NW == KC && KPW % 2 == 0 && PPW * 2 == KPW, "lm attn W8: a w
 
 DEV void la_stamp(const LmAttnArgs& a, int k) { hl_stamp(a.stamps, blockIdx.x, k, 0); }
 
-template <bool W8, int KVQ>
+// Phase 2 of the long form (LONG, bf16 KV): the attention units of workgroup w's wave.  Unit u of pair
+// p = (row, kv head) covers keys [cu, ue) = 32 s keys, s = la_unit_steps(len) from the row's own length; the
+// wave runs the short form's 32-key step over them, carrying (m, l, O): m = max(m, step max), alpha =
+// e^{m_old - m} on l and on O (the P.V MFMA's C operand).  From (-inf, 0, 0) the first step's alpha is 0
+// and its results are the short form's, bit for bit, so a unit of one step (every row of <= 4,096 keys)
+// writes the partial the short form writes.  The next step's K fragments load under this step's MFMAs
+// (two K sets in turn); V loads at the step's start.
+DEV void la_long_units(const LmAttnArgs& a, const int* pre, bf16* xs, bf16* pt, int R, int w, int wave, int lane) {
+  using namespace la;
+  const RopeEpi& RP = a.qkv.rope;
+  const int r16 = lane & 15, g4 = lane >> 4;
+  const int U = pre[2 * R];
+  for (int u = w + GRID * wave; u < U; u += GRID * NW) {
+    int p = 0;
+    while (pre[p + 1] <= u) ++p;
+    const int qi = p / NKV, kh = p - qi * NKV;
+    const int len = RP.pos[qi] + 1, s = la_unit_steps(len);
+    const int cu = __builtin_amdgcn_readfirstlane((u - pre[p]) * 32 * s);
+    const int ue = __builtin_amdgcn_readfirstlane(min(len, cu + 32 * s));
+    const long long cbase = (long long)RP.layer * RP.kv.s_layer + (long long)RP.slots[qi] * RP.kv.s_slot +
+                            (long long)kh * RP.kv.s_head;
+    const bf16* K = RP.kv.k + cbase;
+    const bf16* VB = RP.kv.v + cbase;
+    bf16x8 qf[4];
+    const bf16* qrow = RP.q_out + (long long)qi * NH * D + (kh * G + min(r16, G - 1)) * D + 8 * g4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) qf[c] = MemWT::ld16(qrow + 32 * c);
+    if (r16 >= G) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) qf[c] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    float mv[4], lv[4];
+    f32x4 o[8];   // lane: O[head 4 g + i][dim 16 j + r]
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      mv[i] = -INFINITY;
+      lv[i] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bf16* ptw = pt + wave * 512;
+    // keys c0 + 16 tt + r of a step (clamped like the short form's: masked columns read a valid row)
+    auto ldk = [&](int c0, bf16x8(&kf)[2][4]) __attribute__((always_inline)) {
+      const int w1 = min(len, c0 + 32);
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        const int key = min(c0 + 16 * tt + r16, w1 - 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) kf[tt][c] = hl_ldnt(K + (long long)key * D + 32 * c + 8 * g4);
+      }
+    };
+    // one step on the K set `kf`; `kn` takes the next step's K when there is one
+    auto step = [&](int c0, bf16x8(&kf)[2][4], bf16x8(&kn)[2][4]) __attribute__((always_inline)) {
+      const int w1 = min(len, c0 + 32);
+      bf16x8 vf[8];
+      const int kb = min(c0 + 8 * g4, (w1 - 1) & ~7);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vf[j] = hl_ldnt(VB + v_off(16 * j + r16, kb));
+      if (c0 + 32 < ue) ldk(c0 + 32, kn);
+      if (c0 + 32 > w1) {   // the row's tail step: keys kb + e >= w1 contribute nothing
+        const int kb2 = c0 + 8 * g4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) vf[j][e] = kb2 + e < w1 ? vf[j][e] : (bf16)0.f;
+      }
+      f32x4 sacc[2];   // lane: S[head 4 g + i][key c0 + 16 tt + r]
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        sacc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sacc[tt] = mfma16(qf[c], kf[tt][c], sacc[tt]);
+      }
+      float pp[2][4], al[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {   // (the step holds a valid key, so its max is finite)
+        const float s0 = c0 + r16 < w1 ? sacc[0][i] * a.scale : -INFINITY;
+        const float s1 = c0 + 16 + r16 < w1 ? sacc[1][i] * a.scale : -INFINITY;
+        const float mx = fmaxf(mv[i], row16_max(fmaxf(s0, s1)));
+        al[i] = __expf(mv[i] - mx);
+        pp[0][i] = __expf(s0 - mx);
+        pp[1][i] = __expf(s1 - mx);
+        lv[i] = lv[i] * al[i] + row16_sum(pp[0][i] + pp[1][i]);
+        mv[i] = mx;
+      }
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)pp[tt][i];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      const bf16x8 pa = *(const bf16x8*)(ptw + r16 * 32 + 8 * g4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        f32x4 oc;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) oc[i] = o[j][i] * al[i];
+        o[j] = mfma16(pa, vf[j], oc);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the P tile read before the next step writes it
+    };
+    bf16x8 ka[2][4], kb_[2][4];
+    ldk(cu, ka);
+    for (int c0 = cu; c0 < ue; c0 += 64) {
+      step(c0, ka, kb_);
+      if (c0 + 32 >= ue) break;
+      step(c0 + 32, kb_, ka);
+    }
+    // the unit's partial, as the short form writes it: O through this wave's 3 KB of LDS, then (m, l) per head
+    float* pu = a.part + (long long)u * PART;
+    float* ow = (float*)xs + wave * (G * D);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int h = 4 * g4 + i;
+      if (h < G) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ow[h * D + 16 * j + r16] = o[j][i];
+        if (r16 == 0) {
+          const float2 mlv = make_float2(mv[i], lv[i]);
+          __hip_atomic_store((gu64*)(pu + G * D + 2 * h), __builtin_bit_cast(unsigned long long, mlv),
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int q = 0; q < G * D / 256; ++q) {
+      const f32x4 v4 = *(const f32x4*)(ow + (q * 64 + lane) * 4);
+      const u64x2 uv = __builtin_bit_cast(u64x2, v4);
+      __hip_atomic_store((gu64*)(pu + (q * 64 + lane) * 4), uv[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store((gu64*)(pu + (q * 64 + lane) * 4 + 2), uv[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads done before the next unit's writes
+  }
+}
+
+template <bool W8, int KVQ, bool LONG = false>
 __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   using namespace la;
+  static_assert(!LONG || KVQ == 0, "the long form reads a bf16 cache");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16* xs = (bf16*)(smem + XS);        // phase 1: [16][XST] A rows; phase 4: attention rows
   float* red = (float*)(smem + RED);    // [8 waves][256] MFMA partials
@@ -118,6 +263,9 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   int nunit = 0;
   if (threadIdx.x < 2 * RMAX) {
     const int qi = threadIdx.x / NKV;
+    if constexpr (LONG)   // ceil(len / (32 s)) units of s = la_unit_steps(len) steps: the same units while len <= 4,096
+      nunit = qi < R ? la_unit_count(RP.pos[qi] + 1) : 0;
+    else
     nunit = qi < R ? (RP.pos[qi] + 1 + 31) / 32 : 0;
   }
   int ts = 0, tp = 0;   // KVQ: row threadIdx.x's slot and position (rows >= R repeat R - 1)
@@ -318,6 +466,10 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   }
 
   // ================= phase 2: attention units (row, kv head, 32 keys), one wave each
+  // (LONG: units of 32 s keys, la_long_units above)
+  if constexpr (LONG) {
+    la_long_units(a, pre, xs, pt, R, w, wave, lane);
+  } else {
   const int U = pre[2 * R];
   for (int u = w + GRID * wave; u < U; u += GRID * NW) {
     int p = 0;
@@ -563,6 +715,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads done before the next unit's writes
   }
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   la_stamp(a, 4);
   __syncthreads();
@@ -660,20 +813,30 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
 
 static bool la_shape_ok(int H, int nh, int nkv, int d, int R, int keys) {
   return H == la::H && nh == la::NH && nkv == la::NKV && d == la::D && R >= 1 && R <= la::RMAX && keys >= 1 &&
-         keys <= LA_MAX_KEYS;
+         keys <= LA_LONG_MAX_KEYS;
 }
+// (a pass planned past LA_MAX_KEYS runs the long instantiation: its own residency; bf16 KV only)
+static bool la_long(int keys) { return keys > LA_MAX_KEYS; }
 bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys) {
   if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  if (la_long(keys)) {
+    static const bool okl = persist_resident_kernel((const void*)k_lm_attn<false, 0, true>, la::NT, la::TOTAL, la::GRID);
+    return okl;
+  }
   static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false, 0>, la::NT, la::TOTAL, la::GRID);
   return ok;
 }
 bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys) {
   if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  if (la_long(keys)) {
+    static const bool okl = persist_resident_kernel((const void*)k_lm_attn<true, 0, true>, la::NT, la::TOTAL, la::GRID);
+    return okl;
+  }
   static const bool ok = persist_resident_kernel((const void*)k_lm_attn<true, 0>, la::NT, la::TOTAL, la::GRID);
   return ok;
 }
 bool lm_attn_kvq_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys) {
-  if (!la_shape_ok(H, nh, nkv, d, R, keys)) return false;
+  if (!la_shape_ok(H, nh, nkv, d, R, keys) || la_long(keys)) return false;   // (the KVQ forms are short only)
   if (kvq == 1 && !w8) {
     static const bool ok = persist_resident_kernel((const void*)k_lm_attn<false, 1>, la::NT, la::TOTAL, la::GRID);
     return ok;
@@ -689,7 +852,17 @@ bool lm_attn_kvq_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, in
   return false;
 }
 
-size_t lm_attn_part_floats(int R, int keys) { return (size_t)R * la::NKV * ((keys + 31) / 32) * la::PART; }
+// (the most units of any row of <= keys keys: la_unit_count is not monotonic past LA_MAX_KEYS, where a
+// row of LA_MAX_KEYS keys holds the maximum, LA_MAX_KEYS / 32)
+size_t lm_attn_part_floats(int R, int keys) {
+  return (size_t)R * la::NKV * (((keys < LA_MAX_KEYS ? keys : LA_MAX_KEYS) + 31) / 32) * la::PART;
+}
+extern "C" int vv_diag_lm_attn_plan(int len, int* out) {
+  if (len < 1 || len > LA_LONG_MAX_KEYS || !out) return 1;
+  out[0] = la_unit_steps(len);
+  out[1] = la_unit_count(len);
+  return 0;
+}
 
 // the W8 form when a code pointer is set (all four of q|k|v's and o_proj's codes and exponents, or it is an
 // error); the KV form from a.kvq (1: the FP8 cache a.kv8; 2: the diagnostic round trip, bf16 weights only),
@@ -711,7 +884,10 @@ int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st) {
       !a.sync || !a.err)
     return 3;
   const dim3 grid(la::GRID), blk(la::NT);
-  if (kvq == 1 && w8) hipLaunchKernelGGL((k_lm_attn<true, 1>), grid, blk, la::TOTAL, st, a);
+  if (la_long(keys)) {   // the long form exactly when the pass is planned past LA_MAX_KEYS (kvq != 0: no fit above)
+    if (w8) hipLaunchKernelGGL((k_lm_attn<true, 0, true>), grid, blk, la::TOTAL, st, a);
+    else hipLaunchKernelGGL((k_lm_attn<false, 0, true>), grid, blk, la::TOTAL, st, a);
+  } else if (kvq == 1 && w8) hipLaunchKernelGGL((k_lm_attn<true, 1>), grid, blk, la::TOTAL, st, a);
   else if (kvq == 1) hipLaunchKernelGGL((k_lm_attn<false, 1>), grid, blk, la::TOTAL, st, a);
   else if (kvq == 2) hipLaunchKernelGGL((k_lm_attn<false, 2>), grid, blk, la::TOTAL, st, a);
   else if (w8) hipLaunchKernelGGL((k_lm_attn<true, 0>), grid, blk, la::TOTAL, st, a);

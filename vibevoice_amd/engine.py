@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
+from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
                       pack)
 
 _VALID_IDS_DEFAULT = None
@@ -77,7 +77,8 @@ class Engine:
 
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
-                 persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False):
+                 persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False,
+                 lm_attn_max_keys=None):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -101,7 +102,15 @@ class Engine:
         o_proj launches).  Needs FP8 weights, tp_size 1 and a bf16 KV cache (or lm_attn_kv8).
         lm_attn_kv8: True runs the one-launch LM attention kernel on the FP8 KV cache
         (vv_set_lm_attn_kv8; default off: an FP8-KV engine runs the q|k|v, quantise,
-        attention and o_proj launches).  Needs kv_dtype="fp8_e4m3" and tp_size 1."""
+        attention and o_proj launches).  Needs kv_dtype="fp8_e4m3" and tp_size 1.
+        lm_attn_max_keys: None = decode passes planned past 4,096 keys (a captured graph is
+        planned at max_ctx) run the q|k|v, attention and o_proj launches; an int in
+        [4096, max_ctx] runs them in the one-launch kernel's long form
+        (vv_set_lm_attn_max_keys; rows of at most 4,096 keys compute the same bits; bf16 KV --
+        an FP8-KV engine keeps its own launches past 4,096 keys).  tp_size 1 only.  Measured
+        at B = 1: no context up to 65,536 keys at which the three
+        launches win; at 16 full-length rows they are 3 us per layer ahead near 8K keys."""
+        self.lm_attn_max_keys = check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
         persistent = normalize_persistent(persistent)
         check_weight_dtype(weight_dtype, tp_size)
         check_kv_dtype(kv_dtype, tp_size)
@@ -149,6 +158,8 @@ class Engine:
                 _lib.check(L.vv_set_lm_attn_w8(h, 1), "set_lm_attn_w8")
             if self.lm_attn_kv8:
                 _lib.check(L.vv_set_lm_attn_kv8(h, 1), "set_lm_attn_kv8")
+            if self.lm_attn_max_keys is not None:
+                _lib.check(L.vv_set_lm_attn_max_keys(h, self.lm_attn_max_keys), "set_lm_attn_max_keys")
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")

@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .engine import Engine
-from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
+from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
 
 
 @dataclass
@@ -174,7 +174,7 @@ class VibeVoiceTokenConstraintProcessor:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VibeVoiceConfig, state_dict, device="cuda", attn_implementation="hip",
                  max_batch=8, max_ctx=8192, tp_group=None, tp_head=None, persistent=True, weight_dtype=None,
-                 kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False):
+                 kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False, lm_attn_max_keys=None):
         """tp_group: a torch.distributed process group whose ranks (one per GPU)
         tensor-parallel-shard the Qwen2 backbone over RCCL; every
         rank then runs generate() on the same inputs (SPMD) and gets the same
@@ -196,7 +196,20 @@ class VibeVoiceForConditionalGenerationInference:
         and no tensor-parallel group, else ValueError; INTEGRATION.md §2 "Weight formats").
         lm_attn_kv8: True runs the one-launch LM attention kernel on the FP8 KV cache
         (default off; needs kv_dtype="fp8_e4m3" and no tensor-parallel group, else
-        ValueError; INTEGRATION.md §2 "Capacity / KV formats")."""
+        ValueError; INTEGRATION.md §2 "Capacity / KV formats").
+        lm_attn_max_keys: None (the default) keeps the one-launch LM attention kernel to
+        decode passes planned at 4,096 keys or fewer -- generate() plans its captured
+        graphs at max_ctx, so with max_ctx > 4,096 the q|k|v, attention and o_proj
+        launches run from the first frame.  An int in [4096, max_ctx] runs those passes
+        in the kernel's long form (rows of at most 4,096 keys compute the same bits; no
+        tensor-parallel group, else ValueError; bf16 KV -- with kv_dtype="fp8_e4m3" passes
+        past 4,096 keys keep their launches).  Measured (DESIGN.md §3 "k_lm_attn past 4,096
+        keys"): at B = 1 the default max_ctx=8192 steps in 2.46 ms with it against 2.62
+        without, and no context up to 65,536 keys favours the three launches; at B = 8 with
+        every row near 8K keys the three launches are about 3 us per layer ahead."""
+        max_ctx = min(max_ctx, config.decoder_config.max_position_embeddings)
+        check_lm_attn_max_keys(lm_attn_max_keys, max_ctx)
+        self.lm_attn_max_keys = lm_attn_max_keys
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
         check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
@@ -218,6 +231,7 @@ class VibeVoiceForConditionalGenerationInference:
             check_kv_dtype(kv_dtype, tp_size)
             check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
             check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size, lm_attn_kv8=lm_attn_kv8)
+            check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
             if tp_size > 1:
                 box = [Engine.tp_unique_id() if tp_rank == 0 else None]
                 dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
@@ -225,12 +239,13 @@ class VibeVoiceForConditionalGenerationInference:
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.tp_head = head_tp_default(config, tp_size) if tp_head is None else bool(tp_head and tp_size > 1)
         self.engine = Engine(config, state_dict, self.device, max_batch=max_batch, tp_head=self.tp_head,
-                             max_ctx=min(max_ctx, config.decoder_config.max_position_embeddings),
+                             max_ctx=max_ctx,
                              tp_rank=tp_rank, tp_size=tp_size, tp_unique_id=uid, persistent=persistent,
                              **({} if weight_dtype is None else {"weight_dtype": weight_dtype}),
                              **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
                              **({"lm_attn_w8": True} if lm_attn_w8 else {}),
-                             **({"lm_attn_kv8": True} if lm_attn_kv8 else {}))
+                             **({"lm_attn_kv8": True} if lm_attn_kv8 else {}),
+                             **({} if lm_attn_max_keys is None else {"lm_attn_max_keys": lm_attn_max_keys}))
         self.ddpm_inference_steps = config.diffusion_head_config.ddpm_num_inference_steps
         self.model = _ModelView(self)
         self.use_graphs = True          # capture the steady-state loop body into hipGraphs
@@ -279,7 +294,7 @@ class VibeVoiceForConditionalGenerationInference:
     @classmethod
     def from_pretrained(cls, path, torch_dtype=torch.bfloat16, device_map="cuda", attn_implementation="hip",
                         synthetic_seed=0, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False,
-                        **kw):
+                        lm_attn_max_keys=None, **kw):
         """`path`: a checkpoint dir (config.json + *.safetensors), or
         "synthetic:1.5B" / "synthetic:Large" for seeded random weights at the
         real shapes (no checkpoints are reachable offline).
@@ -293,11 +308,14 @@ class VibeVoiceForConditionalGenerationInference:
         quantised from the bf16 checkpoint while loading (no FP8 on-disk format).
         `kv_dtype`: None (bf16) or "fp8_e4m3": the LM's KV cache format.
         `lm_attn_w8`: True runs the one-launch LM attention kernel on FP8 weights.
-        `lm_attn_kv8`: True runs the one-launch LM attention kernel on the FP8 KV cache."""
+        `lm_attn_kv8`: True runs the one-launch LM attention kernel on the FP8 KV cache.
+        `lm_attn_max_keys`: None, or an int in [4096, max_ctx]: decode passes planned up to
+        that many keys run the one-launch LM attention kernel (its long form past 4,096)."""
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
         check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
         check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
+        check_lm_attn_max_keys(lm_attn_max_keys, 1 << 30)   # (the type; the constructor checks the range against its max_ctx)
         resolve_dtype(torch_dtype)
         dev = resolve_device(device_map)
         if str(path).startswith("synthetic:"):
@@ -307,7 +325,8 @@ class VibeVoiceForConditionalGenerationInference:
             cfg = VibeVoiceConfig.from_json_file(os.path.join(path, "config.json"))
             sd = load_state_dict(path, cfg)
         return cls(cfg, sd, dev, attn_implementation=attn_implementation, weight_dtype=weight_dtype,
-                   kv_dtype=kv_dtype, lm_attn_w8=lm_attn_w8, lm_attn_kv8=lm_attn_kv8, **kw)
+                   kv_dtype=kv_dtype, lm_attn_w8=lm_attn_w8, lm_attn_kv8=lm_attn_kv8,
+                   lm_attn_max_keys=lm_attn_max_keys, **kw)
 
     @classmethod
     def _from_config(cls, config, torch_dtype=None, device_map="cuda", attn_implementation="hip", seed=0,

@@ -246,6 +246,26 @@ def check_lm_attn_kv8(lm_attn_kv8, kv_dtype=None, tp_size=1):
     return lm_attn_kv8
 
 
+LM_ATTN_KEYS = 4096   # the one-launch LM attention kernel's short form (kernels.h LA_MAX_KEYS)
+
+
+def check_lm_attn_max_keys(lm_attn_max_keys, max_ctx=LM_ATTN_KEYS, tp_size=1):
+    """Validate `lm_attn_max_keys`: the longest decode pass, in keys, that runs the
+    one-launch LM attention kernel (vv_set_lm_attn_max_keys).  None = the default
+    (4,096: longer passes run the q|k|v, attention and o_proj launches); an int in
+    [4096, max_ctx] lets passes up to that length run the kernel's long form.
+    tp_size 1 only."""
+    if lm_attn_max_keys is None:
+        return None
+    if isinstance(lm_attn_max_keys, bool) or not isinstance(lm_attn_max_keys, int):
+        raise ValueError(f"lm_attn_max_keys={lm_attn_max_keys!r}: expected None or an int")
+    if tp_size > 1:
+        raise ValueError(f"lm_attn_max_keys is not supported with tensor parallelism (tp_size={tp_size})")
+    if not LM_ATTN_KEYS <= lm_attn_max_keys <= max_ctx:
+        raise ValueError(f"lm_attn_max_keys={lm_attn_max_keys} is outside [{LM_ATTN_KEYS}, max_ctx={max_ctx}]")
+    return lm_attn_max_keys
+
+
 def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1, *, lm_attn_kv8=False):
     """The per-engine option that runs the one-launch LM attention kernel on FP8
     weights (vv_set_lm_attn_w8): it needs FP8 weights (`weight_dtype` is the
