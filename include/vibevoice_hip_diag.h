@@ -242,6 +242,12 @@ int vv_lm_attn_kvround(int on);
  * out[1] = units per (row, kv head) (<= 128); the function the kernel itself
  * evaluates per row (kernels.h la_unit_steps / la_unit_count). */
 int vv_diag_lm_attn_plan(int len, int* out);
+/* Diagnostic: the one-launch kernel's form for FP8 weights (w8 0 / 1), the KV form
+ * kvq (0 raw bf16 rows, 1 the FP8 cache, 2 the round-trip diagnostic) and a pass
+ * planned for `keys` keys (1 .. 2^20): 0 and out[0..2] = (w8, kvq, long) when that
+ * form is built (seven are: kvq = 2 with bf16 weights only, kvq != 0 at <= 4,096
+ * keys only), nonzero when it is not; the table the launcher itself looks up. */
+int vv_diag_lm_attn_form(int w8, int kvq, int keys, int* out);
 /* Diagnostic (bench.py): `reps` passes over the LM layers' attention halves alone
  * on ntok decode rows (embeds [ntok][H] as layer 0's input, slots / positions as
  * for vv_lm_forward). */

@@ -257,3 +257,29 @@ def test_persist_decision_rule():
     assert d(1, 256, 64, 256, 1, 1) == 0         # scratch: waves may wait for slots
     assert d(1, 256, 0, 256, 2, 1) == 0          # a second registered context on the device
     assert d(1, 256, 0, 256, 1, 0) == 0          # switched off (VIBEVOICE_PERSISTENT=0 / vv_set_persistent)
+
+
+def test_lm_attn_form_table():
+    """k_lm_attn's seven built forms (lm_attn.hip la_form: the table the launcher looks up): FP8 weights x KV
+    form x short / long.  kvq = 2 (the diagnostic) is built for bf16 weights only and the kvq forms at no more
+    than 4,096 keys: those five combinations, and keys outside 1 .. 2^20, are refused."""
+    f = _lib.lib().vv_diag_lm_attn_form
+    out = (ctypes.c_int * 3)()
+    built = set()
+    for w8 in (0, 1):
+        for kvq in (0, 1, 2):
+            for keys in (1, 4096, 4097, 1 << 20):
+                lng = int(keys > 4096)
+                exists = not (kvq == 2 and w8) and not (kvq != 0 and lng)
+                out[0] = out[1] = out[2] = -1
+                rc = f(w8, kvq, keys, out)
+                assert (rc == 0) == exists, (w8, kvq, keys, rc)
+                if exists:
+                    assert tuple(out) == (w8, kvq, lng), (w8, kvq, keys, tuple(out))
+                    built.add(tuple(out))
+                else:
+                    assert tuple(out) == (-1, -1, -1)
+                assert f(w8, kvq, 0, out) != 0 and f(w8, kvq, (1 << 20) + 1, out) != 0
+    assert built == {(0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 2, 0), (0, 0, 1), (1, 0, 1)}
+    assert sum(f(w8, kvq, keys, out) != 0 for w8 in (0, 1) for kvq in (0, 1, 2) for keys in (4096, 4097)) == 5
+    assert f(0, 0, 1, None) != 0 and f(2, 0, 1, out) != 0 and f(0, 3, 1, out) != 0 and f(0, -1, 1, out) != 0

@@ -27,7 +27,7 @@ from tiny import tiny_config
 from vibevoice_amd import _lib
 from vibevoice_amd.engine import Engine
 from vibevoice_amd.modeling_vibevoice_inference import VibeVoiceForConditionalGenerationInference
-from vibevoice_amd.weights import synthetic_state_dict
+from vibevoice_amd.weights import fake_quantize_state_dict, synthetic_state_dict
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -166,6 +166,54 @@ def test_short_rows_compute_the_short_forms_bits():
     for run in (ra, rb):   # repeat runs
         assert torch.equal(run[1][0], run[2][0]) and torch.equal(run[1][1], run[2][1])
     for (k, v), (k2, v2) in zip(ka, kb):
+        assert k.any() and v.any() and torch.equal(k, k2) and torch.equal(v, v2)
+
+
+# ------------------------------------------------------------------ 2b. FP8 weights, long form
+W8_KEYS = (4093, 4097, 8189)   # keys of each row at step 1: s = 1; s = 2 with a one-key tail unit; s = 2 ending mid-unit
+
+
+def _w8_long_run(eng, rows, xs):
+    """Fill the slots through kv_write, two decode steps planned at 8,192 keys; hidden bits, logits, the appended rows."""
+    L = _lib.lib()
+    R = len(W8_KEYS)
+    for r, (k, v) in enumerate(rows):
+        kv_write(eng, r, 0, k.shape[2], k, v)
+    ar = torch.arange(R).to(**I32)
+    out = []
+    for s in range(2):
+        assert L.vv_lm_attn_active(eng.h, R, 8192) == 1
+        h, lg = eng.lm_forward(xs[s], ar, (torch.tensor(W8_KEYS) - 1 + s).to(**I32), ar, max_pos=8191)
+        torch.cuda.synchronize()
+        out.append((bits(h), lg.cpu()))
+    kv = [tuple(bits(t) for t in kv_read(eng, 2, r, n - 1, n + 1)) for r, n in enumerate(W8_KEYS)]
+    eng.check_sync()
+    assert_counters_consistent(eng)
+    return out, kv
+
+
+def test_w8_long_form_bit_identical_to_bf16_on_dequantised():
+    """k_lm_attn<W8, 0, LONG>: an FP8 engine with lm_attn_w8 and lm_attn_max_keys = 8,192 against a bf16 engine
+    on the dequantised matrices with the same context options (test_gpu_w8_lm_attn.py's bit test, past 4,096 keys)."""
+    cfg = _cfg()
+    sd = _sd(cfg, 191)
+    g = torch.Generator().manual_seed(192)
+    rows = [(torch.randn(2, NKV, n - 1, HD, generator=g).bfloat16(), torch.randn(2, NKV, n - 1, HD, generator=g).bfloat16())
+            for n in W8_KEYS]
+    xs = [torch.randn(len(W8_KEYS), H, generator=g).bfloat16().to(dev) for _ in range(2)]
+    q = _engine(cfg, sd, 2, 8192, lm_attn_max_keys=8192, weight_dtype=FP8, lm_attn_w8=True)
+    assert q.weights_quantized() and _lib.lib().vv_lm_attn_w8(q.h) == 1
+    rq, kq = _w8_long_run(q, rows, xs)
+    _close(q)
+    b = _engine(cfg, fake_quantize_state_dict(sd, cfg), 2, 8192, lm_attn_max_keys=8192)
+    assert not b.weights_quantized()
+    rb, kb = _w8_long_run(b, rows, xs)
+    _close(b)
+    for s, ((h, lg), (hb, lgb)) in enumerate(zip(rq, rb)):
+        print(f"step {s}: {(h != hb).sum().item()} of {h.numel()} hidden values differ")
+        assert torch.isfinite(lg).all() and torch.isfinite(h.view(torch.bfloat16).float()).all()
+        assert torch.equal(h, hb) and torch.equal(lg, lgb)
+    for (k, v), (k2, v2) in zip(kq, kb):
         assert k.any() and v.any() and torch.equal(k, k2) and torch.equal(v, v2)
 
 

@@ -1087,6 +1087,31 @@ int vv_set_valid_ids(vv_ctx* c, int n, const int* ids) {
   return 0;
 }
 
+// diagnostic: a bf16-weight, bf16-KV engine runs k_lm_attn<false, 2> where it would run <false, 0> -- the
+// FP8-KV form's data flow and quantiser on a bf16 cache (the appended rows stored dequantised)
+static std::atomic<int> g_lm_attn_kvround{0};
+extern "C" int vv_lm_attn_kvround(int on) {
+  g_lm_attn_kvround = on ? 1 : 0;
+  return 0;
+}
+// k_lm_attn's form for this context at a pass planned for `keys` keys, decided here only: `one` = false is
+// the three launches (q|k|v, k_attn, o_proj).  w8: every layer's qkv_w and o_w bound as codes with the
+// context's option on (bf16 throughout: the bf16 form; a mixed binding, or codes without the option: the
+// three launches).  kvq: 0 raw rows into a bf16 cache, 1 the FP8 cache with its option (without it: the
+// three launches + k_kv_quant), 2 the diagnostic round trip.  Which (w8, kvq, keys) are built, and
+// resident, is lm_attn_fits' to say.
+struct LmAttnForm {
+  bool one, w8;
+  int kvq;
+};
+static LmAttnForm lm_attn_form(vv_ctx* c, int keys) {
+  const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
+  const bool one = (w8 || c->attn_form == vv_ctx::MLP_BF16) && (!c->kv_dtype || c->lm_attn_kv8) &&
+                   keys <= std::min(c->cfg.max_ctx, c->lm_attn_max_keys);
+  const int kvq = c->kv_dtype ? 1 : g_lm_attn_kvround && c->attn_form == vv_ctx::MLP_BF16 && c->stg.k ? 2 : 0;
+  return {one, w8, kvq};
+}
+
 int vv_finalize(vv_ctx* c) {
   const vv_config& k = c->cfg;
   HIPCHK(hipSetDevice(c->device));
@@ -1181,26 +1206,20 @@ int vv_finalize(vv_ctx* c) {
   // one-launch head layer at 16 rows, ...) counts in the device's registry (hl_register)
   // (the one-launch MLP kernels in the form the MLP weights are bound in; a mixed binding runs neither)
   const bool mlp_w8 = c->mlp_form == vv_ctx::MLP_W8, mlp_one = c->mlp_form != vv_ctx::MLP_MIXED;
-  const bool lf_fits = mlp_one && (mlp_w8 ? lm_ffn_w8_fits(k.hidden, k.intermediate, 2) : lm_ffn_fits(k.hidden, k.intermediate, 2));
-  const bool lf16_fits =
-      mlp_one && (mlp_w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, 16) : lm_ffn16_fits(k.hidden, k.intermediate, 16));
+  const bool lf_fits = mlp_one && lm_ffn_fits(mlp_w8, k.hidden, k.intermediate, 2);
+  const bool lf16_fits = mlp_one && lm_ffn16_fits(mlp_w8, k.hidden, k.intermediate, 16);
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
   const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, c->lm_attn_max_keys);
-  // (the W8 form's own residency where this context will run it: codes throughout + its option)
-  // (... and the FP8-KV form's where an FP8-KV context's option selects it)
-  const bool la_w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
-  const bool la_kv8 = c->kv_dtype && c->lm_attn_kv8;
-  // (the short form's residency, and with lm_attn_max_keys past LA_MAX_KEYS the long form's as well, both
-  // queried here: an engine with the option runs the short form for passes planned at <= LA_MAX_KEYS.  The
-  // long form reads a bf16 cache: an FP8-KV engine keeps k_kv_quant + k_attn past LA_MAX_KEYS.)
+  // (the residency of the form this context will run (lm_attn_form): the short form's, and with
+  // lm_attn_max_keys past LA_MAX_KEYS the long form's as well, both queried here: an engine with the option
+  // runs the short form for passes planned at <= LA_MAX_KEYS.  The long form reads a bf16 cache: an FP8-KV
+  // engine keeps k_kv_quant + k_attn past LA_MAX_KEYS.)
   const int la_short = std::min(la_keys, LA_MAX_KEYS);
-  const bool la_fits = (la_kv8  ? lm_attn_kvq_fits(la_w8, 1, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)
-                        : la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)
-                                : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short)) &&
+  const LmAttnForm la_f = lm_attn_form(c, la_short), la_fl = lm_attn_form(c, la_keys);
+  const bool la_fits = la_f.one && lm_attn_fits(la_f.w8, la_f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
-  if (la_fits && la_keys > LA_MAX_KEYS && !la_kv8)
-    (void)(la_w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys)
-                 : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys));
+  if (la_fits && la_keys > LA_MAX_KEYS && la_fl.one)
+    (void)lm_attn_fits(la_fl.w8, la_fl.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys);
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
   HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
@@ -1511,37 +1530,16 @@ extern "C" int vv_lm_attn(int on) {
   g_lm_attn = on & 15;   // bits 1..3 (A/B): clear those LmAttnArgs::variant bits
   return 0;
 }
-// diagnostic: a bf16-weight, bf16-KV engine runs k_lm_attn<false, 2> where it would run <false, 0> -- the
-// FP8-KV form's data flow and quantiser on a bf16 cache (the appended rows stored dequantised)
-static std::atomic<int> g_lm_attn_kvround{0};
-extern "C" int vv_lm_attn_kvround(int on) {
-  g_lm_attn_kvround = on ? 1 : 0;
-  return 0;
-}
 extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launches record [256][16] phase stamps
   g_lm_attn_stamps = (unsigned long long*)buf;
   return 0;
 }
-// k_lm_attn's KV form for this context: 0 raw rows into a bf16 cache, 1 the FP8 cache (its option), 2 the
-// diagnostic round trip; -1: an FP8 cache without the option (the three launches + k_kv_quant)
-static int lm_attn_kvq(vv_ctx* c) {
-  if (c->kv_dtype) return c->lm_attn_kv8 ? 1 : -1;
-  return g_lm_attn_kvround && c->attn_form == vv_ctx::MLP_BF16 && c->stg.k ? 2 : 0;
-}
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  const int kvq = lm_attn_kvq(c);
-  if (kvq < 0) return false;
-  // every layer's qkv_w and o_w bound as bf16, or as codes with the context's option on (the W8
-  // form: its own residency); a mixed binding, or codes without the option: the three launches
-  const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
-  if (c->attn_form != vv_ctx::MLP_BF16 && !w8) return false;
-  return g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
+  const LmAttnForm f = lm_attn_form(c, P.maxp);
+  return f.one && g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
-         P.hm.T >= P.ntok && P.maxp <= std::min(k.max_ctx, c->lm_attn_max_keys) &&
-         (kvq  ? lm_attn_kvq_fits(w8, kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
-          : w8 ? lm_attn_w8_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)
-               : lm_attn_fits(k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp)) &&
+         P.hm.T >= P.ntok && lm_attn_fits(f.w8, f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
          lm_attn_part_floats(P.ntok, P.maxp) * sizeof(float) <= c->la_part.bytes && persist_on(c);
 }
 extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
@@ -1590,7 +1588,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       LmAttnArgs a;
       memset(&a, 0, sizeof(a));
       a.qkv = g;
-      a.kvq = lm_attn_kvq(c);
+      a.kvq = lm_attn_form(c, P.maxp).kvq;
       a.stg = c->stg;
       a.kv8 = c->kv8;
       a.nw = w.in_norm;
@@ -1691,10 +1689,8 @@ static bool lm_ffn_on(vv_ctx* c, const LmPass& P) {
   if (c->mlp_form == vv_ctx::MLP_MIXED) return false;
   const bool w8 = c->mlp_form == vv_ctx::MLP_W8, small = P.ntok <= 2;
   if (w8 && !(g_lm_ffn_w8 & (small ? 1 : 2))) return false;
-  const bool shape = small ? (w8 ? lm_ffn_w8_fits(k.hidden, k.intermediate, P.ntok) : lm_ffn_fits(k.hidden, k.intermediate, P.ntok))
-                           : (g_lm_ffn & 2) == 0 && c->lf_slab.p &&
-                                 (w8 ? lm_ffn16_w8_fits(k.hidden, k.intermediate, P.ntok)
-                                     : lm_ffn16_fits(k.hidden, k.intermediate, P.ntok));
+  const bool shape = small ? lm_ffn_fits(w8, k.hidden, k.intermediate, P.ntok)
+                           : (g_lm_ffn & 2) == 0 && c->lf_slab.p && lm_ffn16_fits(w8, k.hidden, k.intermediate, P.ntok);
   return g_lm_ffn && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && shape && persist_on(c);
 }

@@ -311,12 +311,10 @@ struct LmFfnArgs {
   const unsigned char* dn8;     // down codes [H][F]
   const signed char* dne;       // [H]
 };
-bool lm_ffn_fits(int H, int F, int R);
-bool lm_ffn_w8_fits(int H, int F, int R);   // the W8 form's own residency
+bool lm_ffn_fits(bool w8, int H, int F, int R);   // (the bf16 and the W8 form: each its own residency)
 int launch_lm_ffn(const LmFfnArgs& a, hipStream_t st);
 // the same block at 3 <= R <= 16 rows (k_lm_ffn16: down split by hidden range too, per-group tickets)
-bool lm_ffn16_fits(int H, int F, int R);
-bool lm_ffn16_w8_fits(int H, int F, int R);
+bool lm_ffn16_fits(bool w8, int H, int F, int R);
 int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 
 // ---- the LM attention half at decode in one launch (lm_attn.hip): input_layernorm
@@ -325,7 +323,8 @@ int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 // (row, kv head).  A pass planned past that (up to LA_LONG_MAX_KEYS; the per-engine option
 // vv_set_lm_attn_max_keys) runs the long form: a unit = s steps of 32 keys, s from the row's own length
 // in the kernel, so a row holds at most LA_MAX_KEYS / 32 = 128 units at any length and the merge
-// phase and the partials' workspace are the short form's.
+// phase and the partials' workspace are the short form's.  The short and the long form run one step text
+// (lm_attn.hip la_step), the long one carrying (m, l, O) across a unit's steps.
 constexpr int LA_MAX_KEYS = 4096;
 constexpr int LA_LONG_MAX_KEYS = 1 << 20;
 // steps per unit of a row of `len` keys (1 while len <= LA_MAX_KEYS: the short form's units), and its units
@@ -366,10 +365,9 @@ struct LmAttnArgs {
   KVLayout stg;
   KV8 kv8;
 };
-bool lm_attn_fits(int H, int nh, int nkv, int d, int R, int keys);
-bool lm_attn_w8_fits(int H, int nh, int nkv, int d, int R, int keys);   // the W8 form's own residency
-// the KVQ forms' own residencies: (w8, kvq) = (0, 1), (1, 1), (0, 2)
-bool lm_attn_kvq_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys);
+// the form (w8, kvq, keys > LA_MAX_KEYS) is one of the seven built -- kvq = 2 with bf16 weights only, the kvq
+// forms at <= LA_MAX_KEYS keys only -- the shapes are the kernel's, and that form's kernel is resident
+bool lm_attn_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys);
 size_t lm_attn_part_floats(int R, int keys);
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st);
 

@@ -398,22 +398,21 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
   stamp(9);
 }
 
-bool lm_ffn_fits(int H, int F, int R) {
-  if (H != lf::H || F != lf::F || R < 1 || R > lf::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn<false>, lf::NT, lf::TOTAL, lf::G);
+template <bool W8>
+static bool lf_resident() {   // (each form's own residency, queried on first use)
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn<W8>, lf::NT, lf::TOTAL, lf::G);
   return ok;
 }
-bool lm_ffn_w8_fits(int H, int F, int R) {
+bool lm_ffn_fits(bool w8, int H, int F, int R) {
   if (H != lf::H || F != lf::F || R < 1 || R > lf::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn<true>, lf::NT, lf::TOTAL, lf::G);
-  return ok;
+  return w8 ? lf_resident<true>() : lf_resident<false>();
 }
 
 // the W8 form when the code pointers are set (all four, or it is an error)
 int launch_lm_ffn(const LmFfnArgs& a, hipStream_t st) {
   const bool w8 = a.gu8 != nullptr;
   if (w8 && (!a.gue || !a.dn8 || !a.dne)) return 1;
-  if (!(w8 ? lm_ffn_w8_fits(lf::H, lf::F, a.R) : lm_ffn_fits(lf::H, lf::F, a.R)) || a.ldx < lf::H) return 3;
+  if (!lm_ffn_fits(w8, lf::H, lf::F, a.R) || a.ldx < lf::H) return 3;
   if (w8) hipLaunchKernelGGL(k_lm_ffn<true>, dim3(lf::G), dim3(lf::NT), lf::TOTAL, st, a);
   else hipLaunchKernelGGL(k_lm_ffn<false>, dim3(lf::G), dim3(lf::NT), lf::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
@@ -664,21 +663,20 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
   stamp(9);
 }
 
-bool lm_ffn16_fits(int H, int F, int R) {
-  if (H != lf16::H || F != lf16::F || R < 3 || R > lf16::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16<false>, lf16::NT, lf16::TOTAL, lf16::G);
+template <bool W8>
+static bool lf16_resident() {
+  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16<W8>, lf16::NT, lf16::TOTAL, lf16::G);
   return ok;
 }
-bool lm_ffn16_w8_fits(int H, int F, int R) {
+bool lm_ffn16_fits(bool w8, int H, int F, int R) {
   if (H != lf16::H || F != lf16::F || R < 3 || R > lf16::RMAX) return false;
-  static const bool ok = persist_resident_kernel((const void*)k_lm_ffn16<true>, lf16::NT, lf16::TOTAL, lf16::G);
-  return ok;
+  return w8 ? lf16_resident<true>() : lf16_resident<false>();
 }
 
 int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st) {
   const bool w8 = a.gu8 != nullptr;
   if (w8 && (!a.gue || !a.dn8 || !a.dne)) return 1;
-  if (!(w8 ? lm_ffn16_w8_fits(lf16::H, lf16::F, a.R) : lm_ffn16_fits(lf16::H, lf16::F, a.R)) || a.ldx < lf16::H || !a.slab)
+  if (!lm_ffn16_fits(w8, lf16::H, lf16::F, a.R) || a.ldx < lf16::H || !a.slab)
     return 3;
   if (w8) hipLaunchKernelGGL(k_lm_ffn16<true>, dim3(lf16::G), dim3(lf16::NT), lf16::TOTAL, st, a);
   else hipLaunchKernelGGL(k_lm_ffn16<false>, dim3(lf16::G), dim3(lf16::NT), lf16::TOTAL, st, a);
