@@ -242,6 +242,14 @@ int vv_lm_attn_kvround(int on);
  * out[1] = units per (row, kv head) (<= 128); the function the kernel itself
  * evaluates per row (kernels.h la_unit_steps / la_unit_count). */
 int vv_diag_lm_attn_plan(int len, int* out);
+/* Diagnostic: the key splits of a row of `len` keys (1 .. 2^20) under a decode
+ * attention launch planned as `nsplit` splits (1 .. 256) of >= `chunk` keys (a
+ * multiple of 32), merged in groups of `group` splits (0: no groups): out[0] =
+ * the row's keys per split, out[1] = its active splits, out[2] = the partials
+ * its consumer merges (ceil(active / group); the active splits when group = 0);
+ * the function the attention, merge and o_proj kernels themselves evaluate per
+ * row (attn_dev.h attn_row_splits). */
+int vv_diag_attn_row_splits(int len, int nsplit, int chunk, int group, int* out);
 /* Diagnostic: the one-launch kernel's form for FP8 weights (w8 0 / 1), the KV form
  * kvq (0 raw bf16 rows, 1 the FP8 cache, 2 the round-trip diagnostic) and a pass
  * planned for `keys` keys (1 .. 2^20): 0 and out[0..2] = (w8, kvq, long) when that

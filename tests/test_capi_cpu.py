@@ -244,6 +244,31 @@ def test_attention_pass_plan_rules():
     assert (p["prefill"], p["nsplit"]) == (1, 1)
 
 
+def test_attention_row_splits():
+    """The per-row key-split plan that k_attn, k_attn_merge, k_attn_finish and o_proj's XF_ATTN_MERGE all
+    evaluate (attn_dev.h attn_row_splits, through vv_diag_attn_row_splits): the row's split size is a
+    multiple of 32 and at least the launch's, its active splits cover the row with none to spare, and the
+    grouped count is ceil(active / group) -- equal to the rule stated here in plain Python."""
+    f = _lib.lib().vv_diag_attn_row_splits
+    out = (ctypes.c_int * 3)()
+    lens = list(range(1, 2101)) + [4095, 4096, 4097, 65535, 65536]
+    for nsplit, chunk in ((1, 1024), (8, 32), (8, 64), (64, 1024), (256, 1024)):
+        for group in (0, 2, 16):
+            for n in lens:
+                assert f(n, nsplit, chunk, group, out) == 0
+                ch, nact, nparts = out[0], out[1], out[2]
+                assert ch % 32 == 0 and ch >= chunk, (n, nsplit, chunk, ch)
+                assert 1 <= nact <= nsplit, (n, nsplit, chunk, nact)
+                assert nact * ch >= n > (nact - 1) * ch, (n, nsplit, chunk, ch, nact)
+                want_ch = max(chunk, -(-(-(-n // nsplit)) // 32) * 32)
+                want_nact = -(-n // want_ch)
+                want_parts = -(-want_nact // group) if group else want_nact
+                assert (ch, nact, nparts) == (want_ch, want_nact, want_parts), (n, nsplit, chunk, group)
+    assert f(0, 8, 32, 0, out) != 0 and f(1, 0, 32, 0, out) != 0 and f(1, 257, 32, 0, out) != 0
+    assert f(1, 8, 48, 0, out) != 0 and f(1, 8, 0, 0, out) != 0 and f(1, 8, 32, -1, out) != 0
+    assert f(1, 8, 32, 0, None) != 0
+
+
 def test_persist_decision_rule():
     """The rule every grid-waiting launch applies before it is issued (VERDICT
     r5 item 8; host logic only): the whole one-per-CU grid resident by the

@@ -161,3 +161,49 @@ def test_prefill_attention_scattered_rows():
     ref = reference(q.cpu(), K.cpu(), V.cpu(), slots.cpu(), pos.cpu())
     assert rel_err(outs[0], ref) < 1e-2 and rel_err(outs[1], ref) < 1e-2
     assert rel_err(outs[0], outs[1]) < 1e-2
+
+
+def test_split_merge_forms_agree():
+    """The three places that merge <= 8 split partials (attn_dev.h attn_merge_parts): k_attn's last-arriving
+    workgroup (form 0), a deferred launch's consumer (form 2, here k_attn_finish) and a grouped launch's two
+    levels (form 3, groups of 2), over one cache through vv_diag_attn_ctx, 32-key splits.  254 keys: 8 splits
+    with a 30-key tail; 96: 3 of the 8 active; 33 / 32: either side of a split edge; 1: the single-split early
+    store.  Deferred == in-kernel bit for bit on every row; grouped within the bf16 tolerance of it (a
+    two-level merge rounds differently) and bit-equal to itself on a repeat."""
+    from tiny import tiny_config
+    from vibevoice_amd.engine import Engine
+    from vibevoice_amd.weights import synthetic_state_dict
+    cfg = tiny_config(hidden=1536, layers=1, heads=12, kv_heads=2, inter=256)
+    sd = synthetic_state_dict(cfg, seed=5, device="cpu", mode="test", with_acoustic_encoder=False)
+    eng = Engine(cfg, sd, dev, max_batch=2, max_ctx=256)
+    L = _lib.lib()
+    g = torch.Generator(device=dev).manual_seed(254)
+    for slot in range(4):
+        k = torch.randn(1, 2, 256, 128, device=dev, generator=g).bfloat16()
+        v = torch.randn(1, 2, 256, 128, device=dev, generator=g).bfloat16()
+        _lib.check(L.vv_diag_kv_write(eng.h, slot, 0, 256, P(k), P(v)), "diag_kv_write")
+    lens = [254, 96, 33, 32, 1]
+    q = torch.randn(len(lens), 12 * 128, device=dev, generator=g).bfloat16()
+    slots = torch.tensor([0, 1, 2, 3, 0], device=dev, dtype=torch.int32)
+    pos = torch.tensor([n - 1 for n in lens], device=dev, dtype=torch.int32)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def attend(form):
+        out = torch.full_like(q, float("nan"))
+        _lib.check(L.vv_diag_attn_ctx(eng.h, 0, len(lens), P(q), P(slots), P(pos), form, P(out), st), "diag_attn_ctx")
+        torch.cuda.synchronize()
+        return out
+
+    _lib.check(L.vv_attn_tune(32, 8), "attn_tune")
+    try:
+        inker, defer, group, again = attend(0), attend(2), attend(3), attend(3)
+    finally:
+        L.vv_attn_tune(0, -1)
+        eng.close()
+    assert torch.isfinite(inker.float()).all()
+    for i, n in enumerate(lens):
+        assert torch.equal(defer[i].view(torch.int16), inker[i].view(torch.int16)), n
+        e = rel_err(group[i], inker[i].float().cpu())
+        print(f"grouped vs in-kernel merge, {n} keys: rel L2 {e:.3e}")
+        assert e < 1e-2, (n, e)
+    assert torch.equal(group.view(torch.int16), again.view(torch.int16))

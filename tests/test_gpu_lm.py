@@ -154,7 +154,8 @@ def test_rope_table_bit_identical():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("nrows,chunk,maxpos", [(2, 256, 1790), (12, 256, 1790), (4, 128, 3000)])
+@pytest.mark.parametrize("nrows,chunk,maxpos", [(2, 256, 1790), (12, 256, 1790), (4, 128, 3000),
+                                                (4, 32, 254)])   # 8 splits of 32 keys: the smallest split size
 def test_attn_defer_bit_identical(nrows, chunk, maxpos):
     """Deferred split merge (vv_attn_defer: k_attn leaves every split's partial,
     o_proj's XF_ATTN_MERGE staging merges them) vs the same splits merged inside

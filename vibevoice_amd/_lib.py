@@ -108,6 +108,7 @@ EXPORTS = [
     ("vv_lm_attn_active", I, [P, I, I]),
     ("vv_diag_lm_attn_plan", I, [I, ctypes.POINTER(I)]),
     ("vv_diag_lm_attn_form", I, [I, I, I, ctypes.POINTER(I)]),
+    ("vv_diag_attn_row_splits", I, [I, I, I, I, ctypes.POINTER(I)]),
     ("vv_lm_attn_stamps", I, [P]),
     ("vv_lm_attn_replay", I, [P, I, P, P, P, I, I, P]),
     ("vv_lm_mlp_replay", I, [P, I, P, P, I, P]),

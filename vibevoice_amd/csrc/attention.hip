@@ -14,18 +14,14 @@
 #include <atomic>
 #include <type_traits>
 
+#include "attn_dev.h"
 #include "kernels.h"
-
 
 // ---------------------------------------------------------------- attention
 // Grid (query row x kv head, split); a workgroup of NW waves owns keys [k0, k1)
 // of its split and hands each wave a contiguous sub-range, merged in LDS.  Per
-// wave, 32 keys per step on the matrix cores (mfma 16x16x32 bf16):
-//   S[16 heads x 16 keys] = Q[heads x 128] . K^T   (2 tiles, 4 MFMAs each; the
-//       G <= 8 query heads of the kv head are the rows, padded to 16)
-//   online softmax on S in registers (row = head spread over 16 lanes)
-//   P (bf16, as the reference's eager path rounds it) -> per-wave LDS tile ->
-//   O[heads x 128] += P[heads x 32 keys] . V[32 keys x 128] (8 MFMAs, V^T cache)
+// wave, 32 keys per step on the matrix cores (attn_dev.h attn_step, carried; the
+// G <= 8 query heads of the kv head are the rows, padded to 16).
 // K / V of the next step are prefetched while the current one computes.
 //
 // Splits: one CU takes in K/V at only ~20-30 GB/s (tools/attn_stamps.py: 4
@@ -47,13 +43,6 @@ constexpr int ATT_CHUNK = 1024;       // keys per split (8 waves x 4 steps of 32
 constexpr int ATT_SPLITS_MAX = 256;
 constexpr int ATT_MERGE_IN = 8;       // splits merged inside k_attn
 
-// keys per split of a row with `len` keys: >= a.chunk, and all a.nsplit splits
-// cover len (k_attn and k_attn_merge must agree)
-DEV int row_chunk(const AttnArgs& a, int len) {
-  const int c = (len + a.nsplit - 1) / a.nsplit;
-  return max(a.chunk, (c + ATT_KC - 1) / ATT_KC * ATT_KC);
-}
-
 DEV f32x4 amfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // The softmax row max / sum over an MFMA tile's 16-lane column group are
@@ -73,21 +62,7 @@ DEV void astamp(const AttnArgs& a, int which) {
 }
 
 // ST = the cache's storage type: bf16, or unsigned char for the FP8 (e4m3) cache
-// (kernels.h KV8).  The FP8 form loads a fragment's 8 codes with one 8-byte load,
-// converts them to bf16 in registers (exact, cvt8) and runs the same MFMAs; the
-// rows' power-of-two scales go on the 16 x 16 score tile, not on the operands:
-// the fp32 scores of key column j times 2^eK[j] after Q.K^T, the fp32
-// probabilities of key j times 2^eV[j] before they are rounded to bf16 for P.V.
-// A power of two commutes with both roundings, so the result is bit for bit
-// that of the bf16 form over a cache holding the dequantised values.
-template <class ST>
-struct KvFrag {   // one lane's MFMA operand piece of 8 cached values, as loaded
-  typedef bf16x8 type;
-};
-template <>
-struct KvFrag<unsigned char> {
-  typedef u32x2 type;
-};
+// (kernels.h KV8; attn_dev.h: KvFrag, and where the rows' scales go)
 template <class ST>
 DEV const ST* kv_k(const AttnArgs& a) {
   if constexpr (std::is_same<ST, bf16>::value) return a.kv.k;
@@ -98,8 +73,6 @@ DEV const ST* kv_v(const AttnArgs& a) {
   if constexpr (std::is_same<ST, bf16>::value) return a.kv.v;
   else return a.kv8.v;
 }
-DEV bf16x8 kv_bf(bf16x8 f) { return f; }
-DEV bf16x8 kv_bf(u32x2 f) { return cvt8(f[0], f[1]); }
 // byte i of a dword of int8 exponents
 DEV int exp_at(unsigned w, int i) { return (int)(signed char)(w >> (8 * i)); }
 
@@ -146,8 +119,8 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   const int len = pos_q + 1;
   // this row's split size: >= a.chunk, all nsplit splits cover len; splits past
   // the row's last key exit at once
-  const int chunk = row_chunk(a, len);
-  const int nact = (len + chunk - 1) / chunk;
+  const AttnSplits rs = attn_row_splits(len, a.nsplit, a.chunk, 0);
+  const int chunk = rs.chunk, nact = rs.nact;
   if (split >= nact) return;
   const int k0 = split * chunk;
   const int k1 = min(len, k0 + chunk);
@@ -161,8 +134,6 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   const ST* VB = kv_v<ST>(a) + cbase;         // 32-position blocks of [128][32] (v_off)
   const signed char* EK = F8 ? a.kv8.ek + cbase / d : nullptr;   // [ctx] row exponents
   const signed char* EV = F8 ? a.kv8.ev + cbase / d : nullptr;
-  const bf16x8 z8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-
   f32x4 o[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -174,106 +145,38 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   }
   // K / V fragments of two 32-key steps in flight per wave (two register sets,
   // both issued before the first step computes): a 512-key split (65K context)
-  // is 64 keys per wave, so all of a workgroup's K / V is requested at once
-  frag kA[2][4], vA[8], kB[2][4], vB[8];
-  // FP8: the exponents of a set's score columns, keys c0 + r and c0 + 16 + r (K in byte 0, V in byte 1)
-  int xA[2] = {0, 0}, xB[2] = {0, 0};
-  // Loads are unconditional, from positions clamped into [0, w1): no branch
-  // and no per-load wait.  (Guarded V loads followed by the tail mask compiled
-  // to a branch + s_waitcnt vmcnt(0) after EACH of a step's 8 V loads -- eight
-  // serialized memory round trips per step.)  Keys past w1 are masked where
-  // their values are used: S to -inf (so P = 0) and V to 0 on the tail step
-  // (the clamped rows hold other keys' values, and 0 x NaN would not vanish).
-  auto load = [&](int c0, frag (&kf)[2][4], frag (&vf)[8], int (&xf)[2]) {
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      const int key = min(c0 + 16 * tt + r, w1 - 1);   // B operand of S: col = key
-#pragma unroll
-      for (int c = 0; c < 4; ++c) kf[tt][c] = *(const frag*)(K + (long long)key * d + 32 * c + 8 * g);
-      if constexpr (F8) xf[tt] = (EK[key] & 0xff) | (EV[key] << 8);
-    }
-    const int kb = min(c0 + 8 * g, (w1 - 1) & ~7);      // B operand of O: k = keys kb .. kb+7, col = dim
-#pragma unroll
-    for (int j = 0; j < 8; ++j) vf[j] = *(const frag*)(VB + v_off(16 * j + r, kb));
+  // is 64 keys per wave, so all of a workgroup's K / V is requested at once.
+  // FP8: with the exponents of a set's score columns, keys c0 + r and c0 + 16 + r.
+  // (attn_dev.h: clamped loads, tail masking, the carried step)
+  struct Set {
+    frag k[2][4], v[8];
+    int xk[2] = {0, 0}, xv[2] = {0, 0};
+  } A, B;
+  auto load = [&](int c0, Set& f) {
+    attn_load_k<AttnLdPlain>(K, EK, EV, c0, w1, r, g, f.k, f.xk, f.xv);
+    attn_load_v<AttnLdPlain>(VB, c0, w1, r, g, f.v);
   };
-  if (w0 < w1) load(w0, kA, vA, xA);
-  if (w0 + 32 < w1) load(w0 + 32, kB, vB, xB);
+  if (w0 < w1) load(w0, A);
+  if (w0 + 32 < w1) load(w0 + 32, B);
   if (a.stamps) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     astamp(a, 1);
   }
-  auto step_bf = [&](int c0, const bf16x8 (&kc)[2][4], bf16x8 (&vc)[8], const int (&xc)[2]) {   // vc is masked in place
-    if (c0 + 32 > w1) {   // the wave's tail step (uniform): keys kb + e >= w1 contribute nothing
-      const int kb = c0 + 8 * g;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vc[j][e] = kb + e < w1 ? vc[j][e] : (bf16)0.f;
-    }
-    // S tiles: lane holds S[head 4g+i][key c0 + 16tt + r]
-    f32x4 sacc[2];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      sacc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sacc[tt] = amfma(qf[c], kc[tt][c], sacc[tt]);
-    }
-    float p[2][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (F8) {
-        sacc[0][i] = ldexpf(sacc[0][i], (int)(signed char)xc[0]);
-        sacc[1][i] = ldexpf(sacc[1][i], (int)(signed char)xc[1]);
-      }
-      float s0 = c0 + r < w1 ? sacc[0][i] * a.scale : -INFINITY;
-      float s1 = c0 + 16 + r < w1 ? sacc[1][i] * a.scale : -INFINITY;
-      float mx = fmaxf(s0, s1);
-      mx = row16_max(mx);
-      const float mnew = fmaxf(m[i], mx);
-      const float al = __expf(m[i] - mnew);
-      p[0][i] = __expf(s0 - mnew);
-      p[1][i] = __expf(s1 - mnew);
-      float ps = p[0][i] + p[1][i];
-      ps = row16_sum(ps);
-      l[i] = l[i] * al + ps;
-      m[i] = mnew;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j][i] *= al;
-    }
-    // P -> LDS [head][key] -> A operand (row = head r, k = keys 8g .. 8g+7)
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (F8) pt[wave][4 * g + i][16 * tt + r] = (bf16)ldexpf(p[tt][i], xc[tt] >> 8);
-        else pt[wave][4 * g + i][16 * tt + r] = (bf16)p[tt][i];
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const bf16x8 pa = *(const bf16x8*)&pt[wave][r][8 * g];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = amfma(pa, vc[j], o[j]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  auto step = [&](int c0, frag (&kq)[2][4], frag (&vq)[8], const int (&xc)[2]) {
+  auto step = [&](int c0, Set& f) {
     if constexpr (F8) {   // codes -> bf16 in registers, then the bf16 step
       bf16x8 kc[2][4], vc[8];
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) kc[tt][c] = kv_bf(kq[tt][c]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vc[j] = kv_bf(vq[j]);
-      step_bf(c0, kc, vc, xc);
+      attn_frags_bf16(f.k, f.v, kc, vc);
+      attn_step<true, true>(a.scale, qf, kc, vc, f.xk, f.xv, c0, w1, &pt[wave][0][0], r, g, m, l, o);
     } else {
-      step_bf(c0, kq, vq, xc);
+      attn_step<false, true>(a.scale, qf, f.k, f.v, f.xk, f.xv, c0, w1, &pt[wave][0][0], r, g, m, l, o);
     }
   };
   for (int c0 = w0; c0 < w1; c0 += 64) {
-    step(c0, kA, vA, xA);
-    if (c0 + 64 < w1) load(c0 + 64, kA, vA, xA);
+    step(c0, A);
+    if (c0 + 64 < w1) load(c0 + 64, A);
     if (c0 + 32 < w1) {
-      step(c0 + 32, kB, vB, xB);
-      if (c0 + 96 < w1) load(c0 + 96, kB, vB, xB);
+      step(c0 + 32, B);
+      if (c0 + 96 < w1) load(c0 + 96, B);
     }
   }
   // this wave's (m, l, O): lane holds O[head 4g+i][dim 16j + r]
@@ -372,76 +275,31 @@ __global__ void __launch_bounds__(64 * NW) k_attn(AttnArgs a) {
   }
   __syncthreads();
   if (!last_flag) return;
-  if (a.group) {
-    // out = the group's (M, L, O): M = max m_s, L = sum e^{m_s - M} l_s, O = sum
-    // e^{m_s - M} o_s in split order (the consumer divides by the merged L)
-    auto ldg = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    constexpr int GMAX = 16;
-    const int ng = gs1 - gs0;
-    for (int e = t; e < G * d; e += 64 * NW) {
-      const int h = e / d, j = e - h * d;
-      const long long p0 = ((long long)qi * a.nh + kh * G + h) * a.nsplit + gs0;
-      float mv[GMAX], lv[GMAX], ov[GMAX];
-#pragma unroll
-      for (int s2 = 0; s2 < GMAX; ++s2) {
-        if (s2 < ng) {
-          mv[s2] = ldg(a.part_ml + (p0 + s2) * 2);
-          lv[s2] = ldg(a.part_ml + (p0 + s2) * 2 + 1);
-          ov[s2] = ldg(a.part_o + (p0 + s2) * d + j);
-        }
-      }
-      float M = -INFINITY;
-#pragma unroll
-      for (int s2 = 0; s2 < GMAX; ++s2)
-        if (s2 < ng) M = fmaxf(M, mv[s2]);
-      float num = 0.f, den = 0.f;
-#pragma unroll
-      for (int s2 = 0; s2 < GMAX; ++s2) {
-        if (s2 < ng) {
-          const float w = __expf(mv[s2] - M);
-          num += w * ov[s2];
-          den += w * lv[s2];
-        }
-      }
-      const long long q0 = ((long long)qi * a.nh + kh * G + h) * a.ngroups + gi;
-      a.part_o2[q0 * d + j] = num;
+  // the last arriver merges splits [gs0, gs1) in order (attn_dev.h attn_merge_parts): a group's
+  // (M, L, O) into its group partial (the consumer divides by the merged L), else the row's output
+  for (int e = t; e < G * d; e += 64 * NW) {
+    const int h = e / d, j = e - h * d;
+    const long long hq = (long long)qi * a.nh + kh * G + h, p0 = hq * a.nsplit + gs0;
+    auto ld = [&](int s2, float& ms, float& ls, float(&os)[1]) __attribute__((always_inline)) {
+      ms = __hip_atomic_load(a.part_ml + (p0 + s2) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ls = __hip_atomic_load(a.part_ml + (p0 + s2) * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      os[0] = __hip_atomic_load(a.part_o + (p0 + s2) * d + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    float M, num[1], den;
+    if (a.group) {
+      attn_merge_parts<16>(gs1 - gs0, ld, M, num, den);
+      const long long q0 = hq * a.ngroups + gi;
+      a.part_o2[q0 * d + j] = num[0];
       if (j == 0) {
         a.part_ml2[q0 * 2] = M;
         a.part_ml2[q0 * 2 + 1] = den;
       }
+    } else {
+      attn_merge_parts<ATT_MERGE_IN>(nact, ld, M, num, den);
+      a.out[hq * d + j] = tobf(num[0] / den);
     }
-    return;
   }
-  // merge the splits: out = sum_s e^{m_s - M} o_s / sum_s e^{m_s - M} l_s
-  auto ld = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  for (int e = t; e < G * d; e += 64 * NW) {
-    const int h = e / d, j = e - h * d;
-    const long long p0 = ((long long)qi * a.nh + kh * G + h) * a.nsplit;
-    float mv[ATT_MERGE_IN], lv[ATT_MERGE_IN], ov[ATT_MERGE_IN];
-#pragma unroll
-    for (int s2 = 0; s2 < ATT_MERGE_IN; ++s2) {
-      if (s2 < nact) {
-        mv[s2] = ld(a.part_ml + (p0 + s2) * 2);
-        lv[s2] = ld(a.part_ml + (p0 + s2) * 2 + 1);
-        ov[s2] = ld(a.part_o + (p0 + s2) * d + j);
-      }
-    }
-    float M = -INFINITY;
-#pragma unroll
-    for (int s2 = 0; s2 < ATT_MERGE_IN; ++s2)
-      if (s2 < nact) M = fmaxf(M, mv[s2]);
-    float num = 0.f, den = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < ATT_MERGE_IN; ++s2) {
-      if (s2 < nact) {
-        const float w = __expf(mv[s2] - M);
-        num += w * ov[s2];
-        den += w * lv[s2];
-      }
-    }
-    a.out[(long long)qi * a.nh * d + (kh * G + h) * d + j] = tobf(num / den);
-  }
-  if (a.stamps) {
+  if (a.stamps && !a.group) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     astamp(a, 3);
   }
@@ -457,8 +315,7 @@ __global__ void __launch_bounds__(512) k_attn_merge(AttnArgs a) {
   __shared__ float sm[NWM], snum[NWM][64], sden[NWM];
   const int qi = blockIdx.x / a.nh, h = blockIdx.x - qi * a.nh;
   const int len = a.pos[qi] + 1;
-  const int chunk = row_chunk(a, len);
-  const int nact = (len + chunk - 1) / chunk;
+  const int nact = attn_row_splits(len, a.nsplit, a.chunk, 0).nact;
   if (nact <= 1) return;                     // k_attn stored this row itself
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int j = blockIdx.y * 64 + lane;
@@ -993,7 +850,7 @@ static int launch_attn_pf(const AttnArgs& a, hipStream_t st) {
 
 // Launch plan for keys up to max_len: splits of ATT_CHUNK keys (at most
 // ATT_SPLITS_MAX; beyond that the splits grow in ATT_CHUNK steps).  Each row
-// sizes its own splits from its length (row_chunk), so a plan made for
+// sizes its own splits from its length (attn_row_splits), so a plan made for
 // max_ctx serves every step of a captured graph.
 static std::atomic<int> g_att_chunk{0}, g_att_merge_in{-1};   // diagnostic overrides (vv_attn_tune)
 extern "C" int vv_attn_tune(int chunk, int merge_in) {
@@ -1070,28 +927,36 @@ __global__ void __launch_bounds__(128) k_attn_finish(AttnArgs a) {
   constexpr int d = 128;
   const int qi = blockIdx.x / a.nh, h = blockIdx.x - qi * a.nh, j = threadIdx.x;
   const int len = a.pos[qi] + 1;
-  const int chunk = row_chunk(a, len);
-  const int nact = (len + chunk - 1) / chunk;
-  const int np = a.group ? (nact + a.group - 1) / a.group : nact;
+  const int np = attn_row_splits(len, a.nsplit, a.chunk, a.group).nparts;   // <= ATT_MERGE_IN (launch_attn)
   const int ld = a.group ? a.ngroups : a.nsplit;
   const float* po = a.group ? a.part_o2 : a.part_o;
   const float* pml = a.group ? a.part_ml2 : a.part_ml;
   const long long p0 = ((long long)qi * a.nh + h) * ld;
-  float M = -INFINITY;
-  for (int s2 = 0; s2 < np; ++s2) M = fmaxf(M, pml[(p0 + s2) * 2]);
-  float num = 0.f, den = 0.f;
-  for (int s2 = 0; s2 < np; ++s2) {
-    const float w = __expf(pml[(p0 + s2) * 2] - M);
-    num += w * po[(p0 + s2) * d + j];
-    den += w * pml[(p0 + s2) * 2 + 1];
-  }
-  a.out[(long long)qi * a.nh * d + h * d + j] = tobf(num / den);
+  float M, num[1], den;
+  attn_merge_parts<ATT_MERGE_IN>(
+      np,
+      [&](int s2, float& ms, float& ls, float(&os)[1]) __attribute__((always_inline)) {
+        ms = pml[(p0 + s2) * 2];
+        ls = pml[(p0 + s2) * 2 + 1];
+        os[0] = po[(p0 + s2) * d + j];
+      },
+      M, num, den);
+  a.out[(long long)qi * a.nh * d + h * d + j] = tobf(num[0] / den);
 }
 int launch_attn_finish(const AttnArgs& a, hipStream_t st) {
   if (a.nq <= 0) return 0;
   if (!a.defer && !a.group) return 1;
   hipLaunchKernelGGL(k_attn_finish, dim3(a.nq * a.nh), dim3(128), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+extern "C" int vv_diag_attn_row_splits(int len, int nsplit, int chunk, int group, int* out) {
+  if (len < 1 || len > (1 << 20) || nsplit < 1 || nsplit > ATT_SPLITS_MAX || chunk < ATT_KC || chunk % ATT_KC || group < 0 || !out) return 1;
+  const AttnSplits s = attn_row_splits(len, nsplit, chunk, group);
+  out[0] = s.chunk;
+  out[1] = s.nact;
+  out[2] = s.nparts;
+  return 0;
 }
 
 int launch_lmhead_ids(int R, int H, const bf16* h, long long ldh, const bf16* W, const int* ids, int nid, float* out,

@@ -1278,7 +1278,7 @@ int vv_finalize(vv_ctx* c) {
   c->kv.k = (bf16*)c->kv_k.p;
   c->kv.v = (bf16*)c->kv_v.p;
   // ---- attention split partials for decode (2 * max_batch rows, <= 64 splits) + tickets
-  CHK(c->attn_part.ensure((size_t)2 * k.max_batch * k.n_heads * 256 * (d + 2) * sizeof(float)));
+  CHK(c->attn_part.ensure(attn_part_bytes((size_t)2 * k.max_batch, k.n_heads, 256, 0)));
   CHK(c->attn_cnt.ensure(65536 * sizeof(unsigned)));
   HIPCHK(hipMemset(c->attn_cnt.p, 0, 65536 * sizeof(unsigned)));
   // ---- split-K slabs + tickets
@@ -1498,7 +1498,7 @@ static int lm_begin(vv_ctx* c, LmPass& P, int ntok, const void* embeds, int embe
   P.ngroups = ap.ngroups;
   if (P.nsplit > 1) {
     if ((size_t)ntok * k.n_kv_heads * std::max(1, P.ngroups) > 65536) FAIL("attention split tickets exhausted");
-    CHK(c->attn_part.ensure((size_t)ntok * k.n_heads * (P.nsplit + P.ngroups) * (d + 2) * sizeof(float)));
+    CHK(c->attn_part.ensure(attn_part_bytes(ntok, k.n_heads, P.nsplit, P.ngroups)));
   }
   // token row m reads embeds row m % embed_rows (the negative CFG rows consume the
   // positive rows' embeddings, :594-596); layer 0's attention residual writes h
@@ -1632,31 +1632,12 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   at.slots = P.slot;
   at.pos = P.pos;
   at.kv = c->kv;
-  at.part_o = (float*)c->attn_part.p;
-  at.part_ml = at.part_o ? at.part_o + (size_t)P.ntok * k.n_heads * P.nsplit * d : nullptr;
   at.group = P.group;
   at.ngroups = P.ngroups;
-  if (P.group) {
-    at.part_o2 = at.part_ml + (size_t)P.ntok * k.n_heads * P.nsplit * 2;
-    at.part_ml2 = at.part_o2 + (size_t)P.ntok * k.n_heads * P.ngroups * d;
-  }
+  attn_part_carve(at, c->attn_part.p);
   KCHK(launch_attn(at, st));
   GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), w.o, EPI_RES, P.hm);
-  if (P.defer) {
-    g.xf.kind = XF_ATTN_MERGE;
-    g.xf.part_o = at.part_o;
-    g.xf.part_ml = at.part_ml;
-    g.xf.qpos = P.pos;
-    g.xf.nsplit = P.nsplit;
-    g.xf.chunk = P.chunk;
-  } else if (P.group) {   // the groups' partials: group g spans keys [g, g + 1) x group x chunk
-    g.xf.kind = XF_ATTN_MERGE;
-    g.xf.part_o = at.part_o2;
-    g.xf.part_ml = at.part_ml2;
-    g.xf.qpos = P.pos;
-    g.xf.nsplit = P.ngroups;
-    g.xf.chunk = P.group * P.chunk;
-  }
+  if (P.defer || P.group) attn_merge_xf(g, at);
   tp_residual(c, g, l == 0 ? P.in_m : P.hm);
   CHK(gemm(c, g, st));
   return 0;
@@ -2785,19 +2766,14 @@ int vv_diag_attn_ctx(vv_ctx* c, int layer, int nq, const void* q, const int* slo
     if (at.nsplit < 2 || at.ngroups > 8) FAIL("vv_diag_attn_ctx: the grouped merge takes 2..16 splits");
   }
   if ((size_t)nq * k.n_kv_heads * std::max(1, at.ngroups) > 65536) FAIL("attention split tickets exhausted");
-  CHK(c->attn_part.ensure((size_t)nq * k.n_heads * (at.nsplit + at.ngroups) * (d + 2) * sizeof(float)));
+  CHK(c->attn_part.ensure(attn_part_bytes(nq, k.n_heads, at.nsplit, at.ngroups)));
   at.counters = (unsigned*)c->attn_cnt.p;
   at.scale = 1.0f / sqrtf((float)d);
   at.q = (const bf16*)q;
   at.out = (bf16*)out;
   at.slots = slots;
   at.pos = pos;
-  at.part_o = (float*)c->attn_part.p;
-  at.part_ml = at.part_o + (size_t)nq * k.n_heads * at.nsplit * d;
-  if (at.group) {
-    at.part_o2 = at.part_ml + (size_t)nq * k.n_heads * at.nsplit * 2;
-    at.part_ml2 = at.part_o2 + (size_t)nq * k.n_heads * at.ngroups * d;
-  }
+  attn_part_carve(at, c->attn_part.p);
   KCHK(launch_attn(at, st));
   if (at.defer || at.group) KCHK(launch_attn_finish(at, st));
   return 0;
@@ -2826,7 +2802,7 @@ int vv_attention_bf16(int nq, int nh, int nkv, const void* q, const void* k_cach
   at.nsplit = at.prefill ? 1 : attn_plan(nq, nkv, max_pos_p1, &chunk);
   if (at.nsplit > 1) {
     if ((size_t)nq * nkv > 65536) FAIL("attention split tickets exhausted");
-    CHK(c->attn_part.ensure((size_t)nq * nh * at.nsplit * (128 + 2) * sizeof(float)));
+    CHK(c->attn_part.ensure(attn_part_bytes(nq, nh, at.nsplit, 0)));
   }
   at.nq = nq;
   at.nh = nh;
@@ -2840,8 +2816,7 @@ int vv_attention_bf16(int nq, int nh, int nkv, const void* q, const void* k_cach
   at.pos = pos;
   at.kv = kv;
   at.counters = (unsigned*)c->attn_cnt.p;
-  at.part_o = (float*)c->attn_part.p;
-  at.part_ml = at.part_o + (size_t)nq * nh * at.nsplit * 128;
+  attn_part_carve(at, c->attn_part.p);
   at.stamps = g_attn_stamps;
   KCHK(launch_attn(at, (hipStream_t)vst));
   return 0;

@@ -39,6 +39,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "attn_dev.h"
 #include "kernels.h"
 #include "gemv_dev.h"
 
@@ -332,10 +333,10 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
     else stage_rw(std::integral_constant<int, 7>(), std::integral_constant<int, 1>(), std::false_type());
   } else if (XF == XF_ATTN_MERGE) {
     // o_proj's A rows = the decode attention output, merged from the key splits'
-    // partials k_attn left (AttnArgs::defer): out = sum_s e^{m_s - M} o_s /
-    // sum_s e^{m_s - M} l_s in split order -- the attention kernel's own merge
-    // term for term (bit-identical), one round trip of partial loads here instead
-    // of a ticket + merge at the attention's tail.  Item (m, 8 dims of head hq).
+    // partials k_attn left (AttnArgs::defer, or its groups' partials): the
+    // attention kernel's own merge (attn_dev.h attn_merge_parts, so bit-identical),
+    // one round trip of partial loads here instead of a ticket + merge at the
+    // attention's tail.  Item (m, 8 dims of head hq).
     const int nsp = a.xf.nsplit;
     // the weight stream first: the merge's two dependent round trips (query
     // length, then the partials) then overlap it instead of preceding it
@@ -345,43 +346,24 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
     for (int e = threadIdx.x; e < a.M * n8; e += NT) {
       const int m = e / n8, k = (e - m * n8) * 8;
       const int hq = k >> 7, j0 = k & 127;
-      const int len = a.xf.qpos[m] + 1;
-      const int cc = (len + nsp - 1) / nsp;
-      const int rch = max(a.xf.chunk, (cc + 31) / 32 * 32);
-      const int nact = (len + rch - 1) / rch;
+      const int np = attn_row_splits(a.xf.qpos[m] + 1, nsp, a.xf.chunk, 0).nact;
       const long long p0 = ((long long)m * (a.K >> 7) + hq) * nsp;
-      float mv[8], lv[8];
-      float4 o0[8], o1[8];
+      float M, num[8], den;
+      attn_merge_parts<8>(
+          np,
+          [&](int s, float& ms, float& ls, float(&os)[8]) __attribute__((always_inline)) {
+            const float2 ml = *(const float2*)(a.xf.part_ml + (p0 + s) * 2);
+            ms = ml.x;
+            ls = ml.y;
+            const f32x4 o0 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0);
+            const f32x4 o1 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0 + 4);
 #pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        if (s < nact) {
-          const float2 ml = *(const float2*)(a.xf.part_ml + (p0 + s) * 2);
-          mv[s] = ml.x;
-          lv[s] = ml.y;
-          o0[s] = *(const float4*)(a.xf.part_o + (p0 + s) * 128 + j0);
-          o1[s] = *(const float4*)(a.xf.part_o + (p0 + s) * 128 + j0 + 4);
-        }
-      }
-      float M = -INFINITY;
-#pragma unroll
-      for (int s = 0; s < 8; ++s)
-        if (s < nact) M = fmaxf(M, mv[s]);
-      float num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, den = 0.f;
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        if (s < nact) {
-          const float w = __expf(mv[s] - M);
-          num[0] += w * o0[s].x;
-          num[1] += w * o0[s].y;
-          num[2] += w * o0[s].z;
-          num[3] += w * o0[s].w;
-          num[4] += w * o1[s].x;
-          num[5] += w * o1[s].y;
-          num[6] += w * o1[s].z;
-          num[7] += w * o1[s].w;
-          den += w * lv[s];
-        }
-      }
+            for (int q = 0; q < 4; ++q) {
+              os[q] = o0[q];
+              os[4 + q] = o1[q];
+            }
+          },
+          M, num, den);
       bf16x8 o8;
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) o8[jj] = tobf(num[jj] / den);

@@ -55,7 +55,7 @@ struct ATransform {
   const float* part_o;   // [M][nh][nsplit][128]
   const float* part_ml;  // [M][nh][nsplit][2]
   const int* qpos;       // [M] query position (row m attends keys 0..qpos[m])
-  int nsplit, chunk;     // the attention launch's plan (row_chunk)
+  int nsplit, chunk;     // the attention launch's plan (attn_dev.h attn_row_splits)
 };
 
 struct RopeEpi {         // EPI_ROPE
@@ -202,6 +202,31 @@ struct AttnArgs {
   float* part_ml2;
   KV8 kv8;              // kv8.k != nullptr: the FP8 cache (kv.k / kv.v unused, kv's strides and max_ctx hold)
 };
+// The partials' workspace of one launch, part_o | part_ml | part_o2 | part_ml2 (d = 128): its bytes
+// for `rows` query rows, and the four pointers of an AttnArgs (nq, nh, nsplit, group, ngroups set)
+// from its base (null: no workspace, a launch of one split)
+inline size_t attn_part_bytes(size_t rows, int nh, int nsplit, int ngroups) {
+  return rows * nh * (nsplit + ngroups) * (128 + 2) * sizeof(float);
+}
+inline void attn_part_carve(AttnArgs& a, void* base) {
+  const size_t n = (size_t)a.nq * a.nh;
+  a.part_o = (float*)base;
+  a.part_ml = base ? a.part_o + n * a.nsplit * 128 : nullptr;
+  a.part_o2 = base && a.group ? a.part_ml + n * a.nsplit * 2 : nullptr;
+  a.part_ml2 = base && a.group ? a.part_o2 + n * a.ngroups * 128 : nullptr;
+}
+// XF_ATTN_MERGE's fields of the consumer's GemmArgs from the attention launch just made: a
+// deferred launch's first level (the splits' partials), a grouped launch's second (group g spans
+// keys [g, g + 1) x group x chunk)
+inline void attn_merge_xf(GemmArgs& g, const AttnArgs& a) {
+  ATransform& xf = g.xf;
+  xf.kind = XF_ATTN_MERGE;
+  xf.part_o = a.group ? a.part_o2 : a.part_o;
+  xf.part_ml = a.group ? a.part_ml2 : a.part_ml;
+  xf.qpos = a.pos;
+  xf.nsplit = a.group ? a.ngroups : a.nsplit;
+  xf.chunk = a.group ? a.group * a.chunk : a.chunk;
+}
 
 // out_r = sum_r in_r for every r (single-process tensor-parallel group)
 struct SumRows {

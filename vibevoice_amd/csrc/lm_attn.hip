@@ -18,27 +18,28 @@
 //      128..223 meanwhile load their o_proj tile (48 KB) into registers, where it
 //      stays until phase 4.
 //   2. attention in units of (row, kv head, 32 keys), one wave each, dealt
-//      round-robin over the 256 workgroups: S = Q.K^T and P.V on MFMA (k_attn's
-//      step, the kv head's 6 query heads padded to 16 rows), the unit's
+//      round-robin over the 256 workgroups: S = Q.K^T and P.V on MFMA (attn_dev.h
+//      attn_step, the kv head's 6 query heads padded to 16 rows), the unit's
 //      (m, l, O) partial written through.
 //   3. one wave per (row, query head) merges its units' partials in unit order
-//      (k_attn's merge formula) into the attention row, written through.
+//      (attn_dev.h's merge formula, online) into the attention row, written through.
 //   4. the o_proj workgroups DMA the attention rows, MFMA with the resident
 //      weights, residual epilogue.
 // Hand-offs: write-through (sc1) stores, each storing wave's vmcnt(0), a
 // workgroup barrier, lane 0's arrival (persist_dev.h hl_grid_wait); readers
 // use sc1 / nt loads (L1-bypassing; MI355X_MICROARCH.md's hand-off table, first
-// row).  Arithmetic: epi_rope's and k_attn's (scores scaled after the MFMA, P
-// rounded to bf16 for P.V, l in fp32), the units merged as k_attn merges splits.
+// row).  Arithmetic: epi_rope's and attn_dev.h's (scores scaled after the MFMA, P
+// rounded to bf16 for P.V, l in fp32; the units merged by its split-merge formula).
 //
 // The kernel is one template, k_lm_attn<W8, KVQ, LONG>, seven instantiations (la_form below), its body
 // four phases and three la_wait()s over force-inlined pieces, each written once:
 //   la_load_tile / la_tile_mfma   a wave's six k-blocks of one 16-row weight tile: the loads (q|k|v, and
 //                                 o_proj at entry or after wait 1) and the MFMAs + `red` store (phases 1, 4)
 //   la_rope_append                phase 1's epilogue: the K slices summed, bias, RoPE, q rows / KV append
-//   la_unit_begin / la_zero_pad_rows / la_load_k / la_load_v / la_step / la_store_partial
+//   la_unit_begin / la_zero_pad_rows / la_store_partial
 //                                 an attention unit: its (row, kv head), cache base and Q fragments; the
-//                                 32-key K / V fragment loads; one 32-key step; the unit's partial
+//                                 unit's partial.  Its 32-key K / V fragment loads and its 32-key step
+//                                 are attn_dev.h's (attn_load_k / attn_load_v with LaLdNT, attn_step)
 //   la_kvq_rows                   the KVQ forms' rows appended by this pass
 //   la_merge                      phase 3
 //
@@ -57,8 +58,8 @@
 // staging cache (slot 0, position = the row index; cos / sin of the real position), as the GEMV
 // epilogues do under FP8 KV.  Phase 2 never uses a cache entry this launch writes: la_kvq_rows takes
 // them from the staged rows through the row quantiser (kv_quant_dev.h).  The K / V fragments load as
-// codes (8 bytes where bf16 loads 16), convert with cvt8 (exact), and the scales go where k_attn's
-// one-byte form puts them (la_step<KV8>): 2^eK[j] on the fp32 score of key j, 2^eV[j] on its fp32
+// codes (8 bytes where bf16 loads 16), convert with cvt8 (exact), and the scales go where attn_dev.h
+// puts them (attn_step<KV8>): 2^eK[j] on the fp32 score of key j, 2^eV[j] on its fp32
 // probability before the bf16 rounding, l from the unscaled probabilities.  No k_kv_stage_prep /
 // k_kv_quant launch, no added wait.  2 = diagnostic (vv_lm_attn_kvround): KVQ = 1's data flow and
 // quantiser on a bf16 cache -- the appended rows stored dequantised, the fragments read as bf16, the
@@ -68,7 +69,7 @@
 // LONG (bf16 KV only; a pass planned past LA_MAX_KEYS keys, which an engine allows with
 // vv_set_lm_attn_max_keys): a unit covers 32 s keys, s = la_unit_steps(len) = ceil(len / 4,096) per
 // row, computed in the kernel from the pass's position table, so a captured graph replays as rows
-// grow across the s edges.  Its wave runs la_step<., CARRY> s times, carrying (m, l, O): m = max(m,
+// grow across the s edges.  Its wave runs attn_step<., CARRY> s times, carrying (m, l, O): m = max(m,
 // step max), alpha = e^{m_old - m} on l and on O (the P.V MFMA's C operand).  The short form's step is
 // the same text with CARRY = false: no carried max, no alpha, a zero C operand.  From (-inf, 0, 0) the
 // first carried step's alpha is 0 and its results are the uncarried step's, bit for bit, so a unit of
@@ -77,6 +78,7 @@
 // partials' workspace do not depend on LONG.
 #include <type_traits>
 
+#include "attn_dev.h"
 #include "kv_quant_dev.h"
 #include "persist_dev.h"
 
@@ -263,93 +265,12 @@ DEV void la_zero_pad_rows(bf16x8 (&qf)[4], int r16) {
   }
 }
 
-// The K fragments of keys c0 + 16 tt + r, and the V fragments of keys c0 + 8 g .., of a step that ends
-// at w1 (clamped: masked columns read a valid row)
-DEV void la_load_k(const bf16* K, int c0, int w1, int r16, int g4, bf16x8 (&kf)[2][4]) {
-  using namespace la;
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt) {
-    const int key = min(c0 + 16 * tt + r16, w1 - 1);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) kf[tt][c] = hl_ldnt(K + (long long)key * D + 32 * c + 8 * g4);
-  }
-}
-DEV void la_load_v(const bf16* VB, int c0, int w1, int r16, int g4, bf16x8 (&vf)[8]) {
-  const int kb = min(c0 + 8 * g4, (w1 - 1) & ~7);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) vf[j] = hl_ldnt(VB + v_off(16 * j + r16, kb));
-}
-
-// One 32-key step of a unit, keys [c0, w1): the tail masking of V, S = Q.K^T, the scale and mask, the row
-// max and sum, the P tile through this wave's LDS tile ptw, the P.V MFMA.  KV8 (KVQ = 1): the keys' row
-// exponents xk / xv, k_attn's one-byte form.  CARRY: (m, l, O) carried from the unit's earlier steps
-// (from (-inf, 0, 0)); otherwise they are this step's alone.
-template <bool KV8, bool CARRY>
-DEV void la_step(float scale, const bf16x8 (&qf)[4], const bf16x8 (&kf)[2][4], bf16x8 (&vf)[8], const int (&xk)[2],
-                 const int (&xv)[2], int c0, int w1, bf16* ptw, int r16, int g4, float (&mv)[4], float (&lv)[4],
-                 f32x4 (&o)[8]) {
-  if (c0 + 32 > w1) {   // the row's tail step: keys kb + e >= w1 contribute nothing
-    const int kb2 = c0 + 8 * g4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vf[j][e] = kb2 + e < w1 ? vf[j][e] : (bf16)0.f;
-  }
-  f32x4 sacc[2];   // lane: S[head 4 g + i][key c0 + 16 tt + r]
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt) {
-    sacc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) sacc[tt] = mfma16(qf[c], kf[tt][c], sacc[tt]);
-  }
-  float pp[2][4], al[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {   // (the step holds a valid key, so its max is finite)
-    if constexpr (KV8) {   // the key's 2^eK on the fp32 score
-      sacc[0][i] = ldexpf(sacc[0][i], xk[0]);
-      sacc[1][i] = ldexpf(sacc[1][i], xk[1]);
-    }
-    const float s0 = c0 + r16 < w1 ? sacc[0][i] * scale : -INFINITY;
-    const float s1 = c0 + 16 + r16 < w1 ? sacc[1][i] * scale : -INFINITY;
-    if constexpr (CARRY) {
-      const float mx = fmaxf(mv[i], row16_max(fmaxf(s0, s1)));
-      al[i] = __expf(mv[i] - mx);
-      pp[0][i] = __expf(s0 - mx);
-      pp[1][i] = __expf(s1 - mx);
-      lv[i] = lv[i] * al[i] + row16_sum(pp[0][i] + pp[1][i]);
-      mv[i] = mx;
-    } else {
-      const float mx = row16_max(fmaxf(s0, s1));
-      pp[0][i] = __expf(s0 - mx);
-      pp[1][i] = __expf(s1 - mx);
-      lv[i] = row16_sum(pp[0][i] + pp[1][i]);
-      mv[i] = mx;
-    }
-  }
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (KV8)   // ... and the key's 2^eV on the fp32 probability before its rounding (l: unscaled)
-        ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)ldexpf(pp[tt][i], xv[tt]);
-      else
-        ptw[(4 * g4 + i) * 32 + 16 * tt + r16] = (bf16)pp[tt][i];
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const bf16x8 pa = *(const bf16x8*)(ptw + r16 * 32 + 8 * g4);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if constexpr (CARRY) {
-      f32x4 oc;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) oc[i] = o[j][i] * al[i];
-      o[j] = mfma16(pa, vf[j], oc);
-    } else {
-      o[j] = mfma16(pa, vf[j], (f32x4){0.f, 0.f, 0.f, 0.f});
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the P tile read before the next step writes it
-}
+// k_lm_attn's K / V fragment loads (attn_dev.h attn_load_k / attn_load_v): global and non-temporal, a
+// fragment's 8 codes as one 8-byte load
+struct LaLdNT {
+  static DEV bf16x8 ld(const bf16* p) { return hl_ldnt(p); }
+  static DEV u32x2 ld(const unsigned char* p) { return hl_ldnt8h(p); }
+};
 
 // Unit u's partial: O[head][dim], then (m, l) per head.  O goes through this wave's 3 KB of LDS (xs is
 // free in phase 2) so that each lane stores whole 16-byte pieces (as 8-byte write-through halves:
@@ -510,14 +431,7 @@ DEV void la_kvq_rows(const LmAttnArgs& a, const int* tslot, const LaUnit& t, int
       }
     }
   }
-  if constexpr (KVQ == 1) {   // codes -> bf16 (exact), then the bf16 step
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) kf[tt][c] = cvt8(kq[tt][c][0], kq[tt][c][1]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) vf[j] = cvt8(vq[j][0], vq[j][1]);
-  }
+  if constexpr (KVQ == 1) attn_frags_bf16(kq, vq, kf, vf);   // codes -> bf16 (exact), then the bf16 step
 }
 
 // Phase 2, short forms: the attention units (row, kv head, 32 keys) of workgroup w's wave.  The unit's K and
@@ -537,30 +451,17 @@ DEV void la_short_units(const LmAttnArgs& a, const int* pre, const int* tslot, b
     u32x2 kq[2][4], vq[8];
     int xk[2] = {0, 0}, xv[2] = {0, 0};
     if constexpr (KVQ == 1) {
-      const unsigned char* K8 = a.kv8.k + t.cbase;
-      const unsigned char* V8 = a.kv8.v + t.cbase;
-      const signed char* EK = a.kv8.ek + t.cbase / D;
-      const signed char* EV = a.kv8.ev + t.cbase / D;
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
-        const int key = min(c0 + 16 * tt + r16, w1 - 1);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) kq[tt][c] = hl_ldnt8h(K8 + (long long)key * D + 32 * c + 8 * g4);
-        xk[tt] = EK[key];
-        xv[tt] = EV[key];
-      }
-      const int kb = min(c0 + 8 * g4, (w1 - 1) & ~7);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vq[j] = hl_ldnt8h(V8 + v_off(16 * j + r16, kb));
+      attn_load_k<LaLdNT>(a.kv8.k + t.cbase, a.kv8.ek + t.cbase / D, a.kv8.ev + t.cbase / D, c0, w1, r16, g4, kq, xk, xv);
+      attn_load_v<LaLdNT>(a.kv8.v + t.cbase, c0, w1, r16, g4, vq);
     } else {
-      la_load_k(RP.kv.k + t.cbase, c0, w1, r16, g4, kf);
-      la_load_v(RP.kv.v + t.cbase, c0, w1, r16, g4, vf);
+      attn_load_k<LaLdNT>(RP.kv.k + t.cbase, nullptr, nullptr, c0, w1, r16, g4, kf, xk, xv);
+      attn_load_v<LaLdNT>(RP.kv.v + t.cbase, c0, w1, r16, g4, vf);
     }
     if constexpr (KVQ != 0) la_kvq_rows<KVQ>(a, tslot, t, c0, w1, R, lane, kf, vf, kq, vq, xk, xv);
     la_zero_pad_rows(qf, r16);
     float mv[4], lv[4];
     f32x4 o[8];   // lane: O[head 4 g + i][dim 16 j + r]
-    la_step<KVQ == 1, false>(a.scale, qf, kf, vf, xk, xv, c0, w1, pt + wave * 512, r16, g4, mv, lv, o);
+    attn_step<KVQ == 1, false>(a.scale, qf, kf, vf, xk, xv, c0, w1, pt + wave * 512, r16, g4, mv, lv, o);
     la_store_partial(a, u, xs, wave, lane, mv, lv, o);
   }
 }
@@ -573,7 +474,7 @@ DEV void la_long_units(const LmAttnArgs& a, const int* pre, bf16* xs, bf16* pt, 
   const RopeEpi& RP = a.qkv.rope;
   const int r16 = lane & 15, g4 = lane >> 4;
   const int U = pre[2 * R];
-  const int x0[2] = {0, 0};
+  int x0[2] = {0, 0};   // bf16 KV: no row exponents
   for (int u = w + GRID * wave; u < U; u += GRID * NW) {
     bf16x8 qf[4];
     const LaUnit t = la_unit_begin(a, pre, u, r16, g4, qf);
@@ -597,12 +498,12 @@ DEV void la_long_units(const LmAttnArgs& a, const int* pre, bf16* xs, bf16* pt, 
     auto step = [&](int c0, bf16x8(&kf)[2][4], bf16x8(&kn)[2][4]) __attribute__((always_inline)) {
       const int w1 = min(len, c0 + 32);
       bf16x8 vf[8];
-      la_load_v(VB, c0, w1, r16, g4, vf);
-      if (c0 + 32 < ue) la_load_k(K, c0 + 32, min(len, c0 + 64), r16, g4, kn);
-      la_step<false, true>(a.scale, qf, kf, vf, x0, x0, c0, w1, ptw, r16, g4, mv, lv, o);
+      attn_load_v<LaLdNT>(VB, c0, w1, r16, g4, vf);
+      if (c0 + 32 < ue) attn_load_k<LaLdNT>(K, nullptr, nullptr, c0 + 32, min(len, c0 + 64), r16, g4, kn, x0, x0);
+      attn_step<false, true>(a.scale, qf, kf, vf, x0, x0, c0, w1, ptw, r16, g4, mv, lv, o);
     };
     bf16x8 ka[2][4], kb[2][4];
-    la_load_k(K, cu, min(len, cu + 32), r16, g4, ka);
+    attn_load_k<LaLdNT>(K, nullptr, nullptr, cu, min(len, cu + 32), r16, g4, ka, x0, x0);
     for (int c0 = cu; c0 < ue; c0 += 64) {
       step(c0, ka, kb);
       if (c0 + 32 >= ue) break;
