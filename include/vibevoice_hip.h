@@ -156,6 +156,20 @@ int vv_lm_attn_kv8(vv_ctx* ctx);
  *   vv_lm_attn_max_keys: the context's option */
 int vv_set_lm_attn_max_keys(vv_ctx* ctx, int keys);
 int vv_lm_attn_max_keys(vv_ctx* ctx);
+/* The most rows of a decode pass that runs the one-launch LM attention kernel (a
+ * decode pass carries 2 B rows: the conditional and CFG rows of B dialogues).
+ * The default, 16, is the kernel's 16-row class; a pass of more rows runs the
+ * q|k|v, attention and o_proj launches.  A larger value (16 .. 32) lets passes of
+ * 17 .. `rows` rows run the kernel's second row class: the same weight tiles over
+ * two 16-row tiles, every row computing the bits it computes in a pass of at most
+ * 16 rows.  bf16 and FP8 weights (vv_set_lm_attn_w8), short and long passes
+ * (vv_set_lm_attn_max_keys); a bf16 KV cache -- an FP8-KV context keeps its
+ * launches above 16 rows whatever the value.  Passes of at most 16 rows are
+ * unaffected.  Callable after vv_create and before vv_finalize; later calls,
+ * values outside 16 .. 32, tensor-parallel engines and a null context are errors.
+ *   vv_lm_attn_max_rows: the context's option (0 for a null context) */
+int vv_set_lm_attn_max_rows(vv_ctx* ctx, int rows);
+int vv_lm_attn_max_rows(vv_ctx* ctx);
 
 /* ids of the constrained vocabulary (speech_start, speech_end, diffusion, eos). */
 int vv_set_valid_ids(vv_ctx* ctx, int n, const int* host_ids);

@@ -256,6 +256,13 @@ int vv_diag_attn_row_splits(int len, int nsplit, int chunk, int group, int* out)
  * form is built (seven are: kvq = 2 with bf16 weights only, kvq != 0 at <= 4,096
  * keys only), nonzero when it is not; the table the launcher itself looks up. */
 int vv_diag_lm_attn_form(int w8, int kvq, int keys, int* out);
+/* ... and for a pass of `rows` rows (1 .. 32): 0 and out[0..3] = (w8, kvq, long,
+ * row tiles) when that form is built.  Eleven are: the seven above at 1 .. 16 rows
+ * (row tiles = 1, vv_diag_lm_attn_form's answers) and, at 17 .. 32 rows (row tiles
+ * = 2; the per-engine option vv_set_lm_attn_max_rows), kvq = 0 with bf16 or FP8
+ * weights, short or long.  Nonzero: kvq != 0 above 16 rows, rows outside 1 .. 32,
+ * a null out. */
+int vv_diag_lm_attn_form_rows(int w8, int kvq, int keys, int rows, int* out);
 /* Diagnostic (bench.py): `reps` passes over the LM layers' attention halves alone
  * on ntok decode rows (embeds [ntok][H] as layer 0's input, slots / positions as
  * for vv_lm_forward). */

@@ -46,6 +46,8 @@ EXPORTS = [
     ("vv_lm_attn_kv8", I, [P]),
     ("vv_set_lm_attn_max_keys", I, [P, I]),
     ("vv_lm_attn_max_keys", I, [P]),
+    ("vv_set_lm_attn_max_rows", I, [P, I]),
+    ("vv_lm_attn_max_rows", I, [P]),
     ("vv_set_schedule", I, [P, I, ctypes.POINTER(F), P, P]),
     ("vv_lm_forward", I, [P, I, P, I, P, P, I, I, P, P, P, P]),
     ("vv_kv_copy", I, [P, I, P, P, P, P]),
@@ -108,6 +110,7 @@ EXPORTS = [
     ("vv_lm_attn_active", I, [P, I, I]),
     ("vv_diag_lm_attn_plan", I, [I, ctypes.POINTER(I)]),
     ("vv_diag_lm_attn_form", I, [I, I, I, ctypes.POINTER(I)]),
+    ("vv_diag_lm_attn_form_rows", I, [I, I, I, I, ctypes.POINTER(I)]),
     ("vv_diag_attn_row_splits", I, [I, I, I, I, ctypes.POINTER(I)]),
     ("vv_lm_attn_stamps", I, [P]),
     ("vv_lm_attn_replay", I, [P, I, P, P, P, I, I, P]),

@@ -254,6 +254,9 @@ struct vv_ctx {
   // the longest pass (keys) the one-launch attention kernel is planned for (vv_set_lm_attn_max_keys before
   // vv_finalize; default LA_MAX_KEYS: the short form only, three launches past it)
   int lm_attn_max_keys = LA_MAX_KEYS;
+  // the most rows of a decode pass the kernel is planned for (vv_set_lm_attn_max_rows before vv_finalize;
+  // default LA_ROWS: the 16-row class only, three launches above it; bf16 KV above 16 rows)
+  int lm_attn_max_rows = LA_ROWS;
   DevBuf w8_scratch; // one dequantised matrix (the largest), bf16: the fallback of launch_gemm
   // FP8 (e4m3) KV cache (kv_fp8.hip; vv_set_kv_dtype before vv_finalize): codes + row
   // exponents instead of kv_k / kv_v; kv keeps the strides (elements) and max_ctx
@@ -1071,6 +1074,17 @@ int vv_set_lm_attn_max_keys(vv_ctx* c, int keys) {
   return 0;
 }
 int vv_lm_attn_max_keys(vv_ctx* c) { return c ? c->lm_attn_max_keys : 0; }
+int vv_set_lm_attn_max_rows(vv_ctx* c, int rows) {
+  if (!c) FAIL("vv_set_lm_attn_max_rows: null context");
+  if (c->finalized) FAIL("vv_set_lm_attn_max_rows after vv_finalize: the attention half's kernels are already chosen");
+  if (c->tp_size > 1 || c->comm) FAIL("vv_set_lm_attn_max_rows is not supported on a tensor-parallel engine");
+  if (rows < LA_ROWS || rows > LA_MAX_ROWS)
+    FAIL("vv_set_lm_attn_max_rows: " + std::to_string(rows) + " is outside [" + std::to_string(LA_ROWS) + ", " +
+         std::to_string(LA_MAX_ROWS) + "]");
+  c->lm_attn_max_rows = rows;
+  return 0;
+}
+int vv_lm_attn_max_rows(vv_ctx* c) { return c ? c->lm_attn_max_rows : 0; }
 int vv_kv_bytes(vv_ctx* c, long long* bytes) {
   if (!c || !bytes) FAIL("vv_kv_bytes: null argument");
   if (!c->finalized) FAIL("vv_kv_bytes before vv_finalize: the KV cache is not allocated yet");
@@ -1094,9 +1108,10 @@ extern "C" int vv_lm_attn_kvround(int on) {
   g_lm_attn_kvround = on ? 1 : 0;
   return 0;
 }
-// k_lm_attn's form for this context at a pass planned for `keys` keys, decided here only: `one` = false is
-// the three launches (q|k|v, k_attn, o_proj).  w8: every layer's qkv_w and o_w bound as codes with the
-// context's option on (bf16 throughout: the bf16 form; a mixed binding, or codes without the option: the
+// k_lm_attn's form for this context at a pass of `rows` rows planned for `keys` keys, decided here only:
+// `one` = false is the three launches (q|k|v, k_attn, o_proj).  Above LA_ROWS rows: with the context's
+// lm_attn_max_rows, raw rows into a bf16 cache only (no KVQ form is built there).
+// w8: every layer's qkv_w and o_w bound as codes with the context's option on (bf16 throughout: the bf16 form; a mixed binding, or codes without the option: the
 // three launches).  kvq: 0 raw rows into a bf16 cache, 1 the FP8 cache with its option (without it: the
 // three launches + k_kv_quant), 2 the diagnostic round trip.  Which (w8, kvq, keys) are built, and
 // resident, is lm_attn_fits' to say.
@@ -1104,11 +1119,12 @@ struct LmAttnForm {
   bool one, w8;
   int kvq;
 };
-static LmAttnForm lm_attn_form(vv_ctx* c, int keys) {
+static LmAttnForm lm_attn_form(vv_ctx* c, int keys, int rows) {
   const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
-  const bool one = (w8 || c->attn_form == vv_ctx::MLP_BF16) && (!c->kv_dtype || c->lm_attn_kv8) &&
-                   keys <= std::min(c->cfg.max_ctx, c->lm_attn_max_keys);
   const int kvq = c->kv_dtype ? 1 : g_lm_attn_kvround && c->attn_form == vv_ctx::MLP_BF16 && c->stg.k ? 2 : 0;
+  const bool one = (w8 || c->attn_form == vv_ctx::MLP_BF16) && (!c->kv_dtype || c->lm_attn_kv8) &&
+                   keys <= std::min(c->cfg.max_ctx, c->lm_attn_max_keys) &&
+                   (rows <= LA_ROWS || (rows <= c->lm_attn_max_rows && kvq == 0));
   return {one, w8, kvq};
 }
 
@@ -1209,18 +1225,28 @@ int vv_finalize(vv_ctx* c) {
   const bool lf_fits = mlp_one && lm_ffn_fits(mlp_w8, k.hidden, k.intermediate, 2);
   const bool lf16_fits = mlp_one && lm_ffn16_fits(mlp_w8, k.hidden, k.intermediate, 16);
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
-  const int la_rows = std::min(2 * k.max_batch, 16), la_keys = std::min(k.max_ctx, c->lm_attn_max_keys);
+  const int la_keys = std::min(k.max_ctx, c->lm_attn_max_keys), la_rows = std::min(2 * k.max_batch, LA_ROWS);
   // (the residency of the form this context will run (lm_attn_form): the short form's, and with
   // lm_attn_max_keys past LA_MAX_KEYS the long form's as well, both queried here: an engine with the option
   // runs the short form for passes planned at <= LA_MAX_KEYS.  The long form reads a bf16 cache: an FP8-KV
   // engine keeps k_kv_quant + k_attn past LA_MAX_KEYS.)
   const int la_short = std::min(la_keys, LA_MAX_KEYS);
-  const LmAttnForm la_f = lm_attn_form(c, la_short), la_fl = lm_attn_form(c, la_keys);
+  const LmAttnForm la_f = lm_attn_form(c, la_short, la_rows), la_fl = lm_attn_form(c, la_keys, la_rows);
   const bool la_fits = la_f.one && lm_attn_fits(la_f.w8, la_f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short) &&
                        c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
   if (la_fits && la_keys > LA_MAX_KEYS && la_fl.one)
     (void)lm_attn_fits(la_fl.w8, la_fl.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys);
-  if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_rows, la_keys) * sizeof(float)));
+  // (the rows the context's lm_attn_max_rows allows above LA_ROWS: that row class's forms are queried as
+  // well, and the partials sized for it; an engine whose form is not built there keeps la_rows)
+  int la_top = la_rows;
+  const int la_wide = std::min(2 * k.max_batch, c->lm_attn_max_rows);
+  if (la_fits && la_wide > LA_ROWS && lm_attn_form(c, la_short, la_wide).one &&
+      lm_attn_fits(la_f.w8, la_f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_wide, la_short)) {
+    la_top = la_wide;
+    if (la_keys > LA_MAX_KEYS && lm_attn_form(c, la_keys, la_wide).one)
+      (void)lm_attn_fits(la_fl.w8, la_fl.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_wide, la_keys);
+  }
+  if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_top, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
   HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
   if (c->head_gemv && head_m16_fits(k.hidden, k.head_ffn, 16))
@@ -1521,7 +1547,7 @@ static void tp_residual(vv_ctx* c, GemmArgs& g, const RowMap& res) {
   }
 }
 
-// the LM attention half at decode in one launch (lm_attn.hip): <= 16 rows of the
+// the LM attention half at decode in one launch (lm_attn.hip): <= 16 rows (the context's lm_attn_max_rows) of the
 // 1.5B shapes, contexts <= the context's lm_attn_max_keys (default LA_MAX_KEYS), unsharded, while the context is the
 // device's only registered one; 0 = the three launches (q|k|v, k_attn, o_proj)
 static std::atomic<int> g_lm_attn{1};
@@ -1536,7 +1562,7 @@ extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launche
 }
 static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
   const vv_config& k = c->cfg;
-  const LmAttnForm f = lm_attn_form(c, P.maxp);
+  const LmAttnForm f = lm_attn_form(c, P.maxp, P.ntok);
   return f.one && g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
          c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
          P.hm.T >= P.ntok && lm_attn_fits(f.w8, f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
@@ -1588,7 +1614,7 @@ static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
       LmAttnArgs a;
       memset(&a, 0, sizeof(a));
       a.qkv = g;
-      a.kvq = lm_attn_form(c, P.maxp).kvq;
+      a.kvq = lm_attn_form(c, P.maxp, P.ntok).kvq;
       a.stg = c->stg;
       a.kv8 = c->kv8;
       a.nw = w.in_norm;
@@ -1687,6 +1713,20 @@ static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, I = k.intermediate;
   const LmLayerW& w = c->lmw[l];
+  if (P.ntok > LA_ROWS && lm_attn_on(c, P)) {
+    // a pass whose attention half ran k_lm_attn's second row class (lm_attn_max_rows): the MLP runs as the
+    // passes of <= LA_ROWS rows it is made of, rows [0, 16) and [16, ntok), each as such a pass runs it
+    // (k_lm_ffn16 / k_lm_ffn where they apply).  The GEMMs of 17 .. 32 rows sum K in another order, so
+    // this is what keeps every row of the pass on the bits it has in a pass of at most 16 rows.
+    for (int r0 = 0; r0 < P.ntok; r0 += LA_ROWS) {
+      LmPass S = P;
+      S.ntok = std::min(LA_ROWS, P.ntok - r0);
+      S.hm = rowmap((bf16*)P.hm.base + (size_t)r0 * H, H);
+      S.act = P.act + (size_t)r0 * I;
+      CHK(lm_mlp_half(c, S, l, st));
+    }
+    return 0;
+  }
   if (lm_ffn_on(c, P)) {
     LmFfnArgs a;
     memset(&a, 0, sizeof(a));

@@ -343,7 +343,7 @@ bool lm_ffn16_fits(bool w8, int H, int F, int R);
 int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 
 // ---- the LM attention half at decode in one launch (lm_attn.hip): input_layernorm
-// -> q|k|v + RoPE + KV append -> attention -> o_proj + residual, R <= 16 rows of
+// -> q|k|v + RoPE + KV append -> attention -> o_proj + residual, R <= 16 rows (<= 32: LA_MAX_ROWS below) of
 // the 1.5B shapes.  Contexts <= LA_MAX_KEYS keys: the short form, an attention unit = 32 keys of one
 // (row, kv head).  A pass planned past that (up to LA_LONG_MAX_KEYS; the per-engine option
 // vv_set_lm_attn_max_keys) runs the long form: a unit = s steps of 32 keys, s from the row's own length
@@ -352,6 +352,13 @@ int launch_lm_ffn16(const LmFfnArgs& a, hipStream_t st);
 // (lm_attn.hip la_step), the long one carrying (m, l, O) across a unit's steps.
 constexpr int LA_MAX_KEYS = 4096;
 constexpr int LA_LONG_MAX_KEYS = 1 << 20;
+// Rows: a pass of <= LA_ROWS rows runs the 16-row class (one 16-row MFMA tile of A rows: MT = 1).  A pass of
+// LA_ROWS + 1 .. LA_MAX_ROWS rows (the per-engine option vv_set_lm_attn_max_rows) runs the second row class,
+// MT = 2: phases 1 and 4 run their one weight tile over two row tiles, each with its own LDS sums, the
+// epilogues on one wave per row tile, the row tables doubled (124 KB of LDS against 82); phases 2 and 3 are
+// per row.  Per row the arithmetic is the 16-row class's.  bf16 KV only: no KVQ form is built at MT = 2,
+// an FP8-KV engine keeps its launches above 16 rows.
+constexpr int LA_ROWS = 16, LA_MAX_ROWS = 32;
 // steps per unit of a row of `len` keys (1 while len <= LA_MAX_KEYS: the short form's units), and its units
 __host__ __device__ constexpr int la_unit_steps(int len) { return len <= LA_MAX_KEYS ? 1 : (len + LA_MAX_KEYS - 1) / LA_MAX_KEYS; }
 __host__ __device__ constexpr int la_unit_count(int len) { return (len + 32 * la_unit_steps(len) - 1) / (32 * la_unit_steps(len)); }
@@ -390,8 +397,9 @@ struct LmAttnArgs {
   KVLayout stg;
   KV8 kv8;
 };
-// the form (w8, kvq, keys > LA_MAX_KEYS) is one of the seven built -- kvq = 2 with bf16 weights only, the kvq
-// forms at <= LA_MAX_KEYS keys only -- the shapes are the kernel's, and that form's kernel is resident
+// the form (w8, kvq, keys > LA_MAX_KEYS, R > LA_ROWS) is one of the eleven built -- kvq = 2 with bf16 weights
+// only, the kvq forms at <= LA_MAX_KEYS keys and <= LA_ROWS rows only -- the shapes are the kernel's, and that
+// form's kernel is resident
 bool lm_attn_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys);
 size_t lm_attn_part_floats(int R, int keys);
 int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st);

@@ -1,7 +1,7 @@
 // The LM attention half at decode in ONE launch (k_lm_attn): input_layernorm ->
 // q|k|v projection (+bias) -> RoPE -> KV append -> GQA attention over the
-// compacted per-row cache -> o_proj -> residual, for R <= 16 query rows of the
-// 1.5B shapes (H 1,536, 12 q / 2 kv heads of 128).
+// compacted per-row cache -> o_proj -> residual, for R <= 16 query rows (17 .. 32: the
+// second row class, MT below) of the 1.5B shapes (H 1,536, 12 q / 2 kv heads of 128).
 // Reference: transformers Qwen2Attention (modeling_qwen2.py:99-134, 150-173,
 // 195-247) as VibeVoiceModel.forward calls it per layer
 // (vibevoice/modular/modeling_vibevoice.py:169-209) inside the generate loop
@@ -31,7 +31,7 @@
 // row).  Arithmetic: epi_rope's and attn_dev.h's (scores scaled after the MFMA, P
 // rounded to bf16 for P.V, l in fp32; the units merged by its split-merge formula).
 //
-// The kernel is one template, k_lm_attn<W8, KVQ, LONG>, seven instantiations (la_form below), its body
+// The kernel is one template, k_lm_attn<W8, KVQ, LONG, MT>, eleven instantiations (la_form below), its body
 // four phases and three la_wait()s over force-inlined pieces, each written once:
 //   la_load_tile / la_tile_mfma   a wave's six k-blocks of one 16-row weight tile: the loads (q|k|v, and
 //                                 o_proj at entry or after wait 1) and the MFMAs + `red` store (phases 1, 4)
@@ -76,6 +76,19 @@
 // one step (every row of <= 4,096 keys) writes the partial the short form writes.  One partial per
 // unit, at most 128 units per (row, kv head): phases 1, 3 and 4, the waits, the stamps and the
 // partials' workspace do not depend on LONG.
+//
+// MT (row tiles of 16 A rows; 2 = a pass of 17 .. 32 rows, which an engine allows with
+// vv_set_lm_attn_max_rows; KVQ = 0 only): the row class.  MT = 1 is the kernel above.  At MT = 2 a q|k|v or
+// o_proj workgroup still loads its one weight tile once (the same six k-blocks per wave, the same loads, the
+// same vmcnt wait) and runs each fragment's MFMA over both row tiles, one accumulator per tile with the
+// k-blocks in MT = 1's order, each tile into its own `red` area; the epilogues (la_rope_append, the residual
+// store) run on one wave per row tile, waves 0 and 1, over their tile's 8 slices in MT = 1's order.  xs holds
+// 32 rows, the unit prefix 2 x 32 + 1 entries, inv_s 32: 124 KB of LDS (la::Lds<2>) against 82, still one
+// workgroup per CU.  Phases 2 and 3, the waits, the stamps and the partial layout are per (row, kv head,
+// unit) and per (row, query head): the same text.  Every value of a row depends on that row's A row, the
+// weights and its own KV entries only, so a row computes the bits it computes in a pass of <= 16 rows
+// (tests/test_gpu_lm_attn_rows.py).  The KVQ forms are not built at MT = 2 (their tables and staged rows are
+// the 16-row class's): an FP8-KV engine keeps its launches above 16 rows.
 #include <type_traits>
 
 #include "attn_dev.h"
@@ -90,18 +103,29 @@ constexpr int PC = KC / 2, PPW = KPW / 2;        // W8: 24 pair blocks per tile,
 constexpr int TQ = NQKV / 16, TO = H / 16;       // 128 q|k|v tiles, 96 o_proj tiles
 constexpr int O0 = TQ;                           // o_proj workgroups [O0, O0 + TO)
 constexpr int XST = H + 8;                       // padded LDS row (elements)
-constexpr int XS = 0, XS_B = RMAX * XST * 2;
-constexpr int RED = XS + XS_B, RED_B = NW * 256 * 4;
-constexpr int PT = RED + RED_B, PT_B = NW * 16 * 32 * 2;
-constexpr int NWS = PT + PT_B, NWS_B = H * 2;              // input_layernorm weight
-constexpr int SM = NWS + NWS_B, SM_B = 64 + 4 * (2 * RMAX + 1) + 12;
-// the KVQ forms' tables: the pass's slots [16], positions [16], and per row the first position this
-// pass appends to the row's slot [16]
-constexpr int KT = SM + SM_B, KT_B = 3 * RMAX * 4;
-// 82 KB: one workgroup per CU (two would share a CU while another idles)
-constexpr int TOTAL = (KT + KT_B) > 82 * 1024 ? (KT + KT_B) : 82 * 1024;
+constexpr int MTMAX = 2;                         // row tiles of 16: the row classes 1..16 (MT = 1) and 17..32 (MT = 2)
+// the LDS carve-up of a row class: MT tiles of 16 A rows
+template <int MT>
+struct Lds {
+  static constexpr int ROWS = 16 * MT;
+  static constexpr int XS = 0, XS_B = ROWS * XST * 2;
+  static constexpr int RED = XS + XS_B, RED_B = MT * NW * 256 * 4;   // one [8 waves][256] area per row tile
+  static constexpr int PT = RED + RED_B, PT_B = NW * 16 * 32 * 2;
+  static constexpr int NWS = PT + PT_B, NWS_B = H * 2;              // input_layernorm weight
+  static constexpr int INV_B = 4 * ROWS;                            // inverse RMS per row
+  static constexpr int SM = NWS + NWS_B, SM_B = INV_B + 4 * (2 * ROWS + 1) + 12;
+  // the KVQ forms' tables: the pass's slots [16], positions [16], and per row the first position this
+  // pass appends to the row's slot [16]
+  static constexpr int KT = SM + SM_B, KT_B = 3 * ROWS * 4;
+  // MT = 1, 82 KB: one workgroup per CU (two would share a CU while another idles).  MT = 2: 124 KB as carved
+  static constexpr int FLOOR = MT == 1 ? 82 * 1024 : 0;
+  static constexpr int TOTAL = (KT + KT_B) > FLOOR ? (KT + KT_B) : FLOOR;
+  static_assert(KT + KT_B <= 160 * 1024 && KT % 16 == 0 && 2 * TOTAL > 160 * 1024, "lm attn LDS");
+};
 constexpr int PART = G * D + 2 * G;              // floats per unit partial: O[6][128], then (m, l) x 6
-static_assert(KT + KT_B <= 160 * 1024 && KT % 16 == 0 && TOTAL == 82 * 1024, "lm attn LDS");
+static_assert(Lds<1>::TOTAL == 82 * 1024 && Lds<1>::ROWS == RMAX && Lds<1>::INV_B == 64, "lm attn LDS: the 16-row class");
+static_assert(RMAX == LA_ROWS && 16 * MTMAX == LA_MAX_ROWS, "the row classes of kernels.h");
+static_assert(NW * G * D * 4 <= Lds<1>::XS_B, "phase 2's partials pass through xs");
 static_assert(GRID == pk::G, "grid waits: 256 arrivals per wait");
 static_assert(KPW * NW == KC && KPW % 2 == 0 && PPW * 2 == KPW, "lm attn W8: a wave's k-blocks are whole pairs");
 // a lane's registers of one weight tile: one 16-byte load each (W8: the 16 code bytes of a pair block)
@@ -144,30 +168,39 @@ DEV void la_load_tile(la::WF<W8> (&wf)[la::NWL<W8>], const bf16* w_bf16, const u
 }
 
 // D[n][m] over this wave's k-blocks into red[wave]: A = the weight tile (row n = lane & 15; W8: code *
-// sc, sc = 2^e of that row), B = the LDS rows xs (column m)
-template <bool W8>
+// sc, sc = 2^e of that row), B = the LDS rows xs (column m).  MT row tiles: the one weight fragment runs
+// over rows 16 t + m of every tile t, each tile its own accumulator (k-blocks in the same order) and its
+// own `red` area [t][wave][256]
+template <bool W8, int MT>
 DEV void la_tile_mfma(const la::WF<W8> (&wf)[la::NWL<W8>], float sc, const bf16* xs, float* red, int wave, int lane) {
   using namespace la;
   const int r16 = lane & 15, g4 = lane >> 4;
-  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kk = 0; kk < KPW; ++kk) {
     const int kc = wave * KPW + kk;   // W8: k-block kc = half kk & 1 of pair kc >> 1
+    bf16x8 wk;
     if constexpr (W8)
-      acc = mfma16(hl_frag8(wf[kk >> 1], kk & 1, sc), *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
+      wk = hl_frag8(wf[kk >> 1], kk & 1, sc);
     else
-      acc = mfma16(wf[kk], *(const bf16x8*)(xs + r16 * XST + kc * 32 + 8 * g4), acc);
+      wk = wf[kk];
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+      acc[t] = mfma16(wk, *(const bf16x8*)(xs + (16 * t + r16) * XST + kc * 32 + 8 * g4), acc[t]);
   }
-  *(f32x4*)(red + wave * 256 + lane * 4) = acc;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) *(f32x4*)(red + (t * NW + wave) * 256 + lane * 4) = acc[t];
 }
 
-// Phase 1's epilogue, wave 0 of q|k|v tile w: the 8 K slices of `red` in order (lane: row m = lane & 15,
-// columns 16 w + 4 g + i), then epi_rope's arithmetic on the prefetched operands (rp / rs: the row's
+// Phase 1's epilogue, one wave per row tile of q|k|v tile w: the 8 K slices of the row tile's `red` in order
+// (lane: row m = m0 + (lane & 15), m0 = 16 x the row tile; columns 16 w + 4 g + i), then epi_rope's arithmetic on the prefetched operands (rp / rs: the row's
 // position and slot, rb4 the bias, cs4 / sn4 the cos / sin row), written through.  KVQ != 0: the K rows
 // and V columns go to the staging cache (slot 0, position = the row index).
 template <int KVQ>
-DEV void la_rope_append(const LmAttnArgs& a, const float* red, int w, int lane, int R, int rp, int rs, bf16x4 rb4,
-                        bf16x4 cs4, bf16x4 sn4) {
+DEV void la_rope_append(const LmAttnArgs& a, const float* red, int w, int lane, int m0, int R, int rp, int rs,
+                        bf16x4 rb4, bf16x4 cs4, bf16x4 sn4) {
   using namespace la;
   const RopeEpi& RP = a.qkv.rope;
   const int r16 = lane & 15, g4 = lane >> 4;
@@ -179,7 +212,7 @@ DEV void la_rope_append(const LmAttnArgs& a, const float* red, int w, int lane, 
     for (int wv = 0; wv < NW; ++wv) s += red[wv * 256 + lane * 4 + i];
     v[i] = s;
   }
-  const int n0 = 16 * w, hh = n0 / D, tt = (n0 % D) >> 4, m = r16;
+  const int n0 = 16 * w, hh = n0 / D, tt = (n0 % D) >> 4, m = m0 + r16;
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = rb(v[i] + bf(rb4[i]));   // q/k/v_proj output (bf16)
   if (hh < NH + NKV) {
@@ -560,19 +593,22 @@ DEV void la_merge(const LmAttnArgs& a, const int* pre, int R, int w, int wave, i
   }
 }
 
-template <bool W8, int KVQ, bool LONG>
+template <bool W8, int KVQ, bool LONG, int MT>
 __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   using namespace la;
+  using L = Lds<MT>;
+  constexpr int ROWS = L::ROWS;
   static_assert(!LONG || KVQ == 0, "the long form reads a bf16 cache");
+  static_assert(MT == 1 || (MT == 2 && KVQ == 0), "the KVQ forms' tables and staged rows are the 16-row class's");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  bf16* xs = (bf16*)(smem + XS);        // phase 1: [16][XST] A rows; phase 4: attention rows
-  float* red = (float*)(smem + RED);    // [8 waves][256] MFMA partials
-  bf16* pt = (bf16*)(smem + PT);        // [8 waves][16][32] P tiles
-  bf16* nw_s = (bf16*)(smem + NWS);
-  float* inv_s = (float*)(smem + SM);   // [16]
-  int* pre = (int*)(smem + SM + 64);    // [2R + 1] unit prefix over (row, kv head) pairs
-  unsigned* ok_s = (unsigned*)(smem + SM + 64 + 4 * (2 * RMAX + 1));
-  int* tslot = (int*)(smem + KT);       // KVQ: [16] the pass's slots, [16] positions, [16] first appended position
+  bf16* xs = (bf16*)(smem + L::XS);        // phase 1: [16 MT][XST] A rows; phase 4: attention rows
+  float* red = (float*)(smem + L::RED);    // [MT row tiles][8 waves][256] MFMA partials
+  bf16* pt = (bf16*)(smem + L::PT);        // [8 waves][16][32] P tiles
+  bf16* nw_s = (bf16*)(smem + L::NWS);
+  float* inv_s = (float*)(smem + L::SM);   // [16 MT]
+  int* pre = (int*)(smem + L::SM + L::INV_B);    // [2R + 1] unit prefix over (row, kv head) pairs
+  unsigned* ok_s = (unsigned*)(smem + L::SM + L::INV_B + 4 * (2 * ROWS + 1));
+  int* tslot = (int*)(smem + L::KT);       // KVQ: [16] the pass's slots, [16] positions, [16] first appended position
   int *tpos = tslot + RMAX, *tmin = tpos + RMAX;
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -580,13 +616,16 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   const int r16 = lane & 15, g4 = lane >> 4;
   const RopeEpi& RP = a.qkv.rope;
   const bool qt = w < TQ, ot = w >= O0 && w < O0 + TO;
+  // the epilogues of phases 1 and 4 run one wave per row tile: wave `et` rows 16 et + (lane & 15)
+  const bool ew = MT == 1 ? wave == 0 : wave < MT;
+  const int et = MT == 1 ? 0 : wave, em = 16 * et + r16;
   unsigned g0 = 0;
   if (threadIdx.x == 0)
     g0 = hl_base_gen(a.sync, pk::GEN_LM_ATTN);
   // the attention units: pair p = row * NKV + kv head holds ceil(len / 32) of
   // them (positions read first: a wait for them then leaves the streams in flight)
   int nunit = 0;
-  if (threadIdx.x < 2 * RMAX) {
+  if (threadIdx.x < 2 * ROWS) {
     const int qi = threadIdx.x / NKV;
     if constexpr (LONG)   // ceil(len / (32 s)) units of s = la_unit_steps(len) steps: the same units while len <= 4,096
       nunit = qi < R ? la_unit_count(RP.pos[qi] + 1) : 0;
@@ -602,8 +641,8 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   }
   la_stamp(a, 0);
   bf16x4 rv_pre = (bf16x4){0, 0, 0, 0};   // o_proj's residual operand (variant 4: loaded at entry)
-  if ((a.variant & 4) && ot && wave == 0 && r16 < R)
-    rv_pre = *(const bf16x4*)(rm_bf(a.res, r16) + 16 * (w - O0) + 4 * g4);
+  if ((a.variant & 4) && ot && ew && em < R)
+    rv_pre = *(const bf16x4*)(rm_bf(a.res, em) + 16 * (w - O0) + 4 * g4);
 
   // ================= phase 1: q|k|v tile (workgroups < 128) / o_proj weights (128..223)
   // W8: the exponent of this lane's row (lane & 15) of this workgroup's tile (q|k|v or o_proj) is loaded
@@ -613,18 +652,18 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   if constexpr (W8)   // (unconditional, clamped: no branch to wait in; read through hl_vopaque where first used)
     ex = ot ? a.owe[16 * (w - O0) + r16] : a.qkv.w8e[16 * min(w, TQ - 1) + r16];
   const int ln = hl_vopaque(lane);
-  // wave 0's RoPE epilogue operands (row m = lane & 15, columns 16 w + 4 g ..): position,
+  // the epilogue waves' RoPE operands (row m = 16 et + (lane & 15), columns 16 w + 4 g ..): position,
   // slot and bias first, the cos / sin row (dependent on the position) after the weights
   int rp = 0, rs = 0;
   bf16x4 rb4 = (bf16x4){0, 0, 0, 0}, cs4 = rb4, sn4 = rb4;
-  if (qt && wave == 0) {
-    const int mm = min(r16, R - 1);
+  if (qt && ew) {
+    const int mm = min(em, R - 1);
     rp = RP.pos[mm];
     rs = RP.slots[mm];
     rb4 = *(const bf16x4*)(a.qkv.epi.bias + 16 * w + 4 * g4);
   }
   if (qt) {
-    const int qn = (a.variant & 1) ? R * 3 : RMAX * 3;
+    const int qn = (a.variant & 1) ? R * 3 : ROWS * 3;
     for (int q = wave; q < qn; q += NW) {   // row q / 3, 64-chunk piece q % 3 (rows >= R re-read R - 1)
       const int m = q / 3, i = q - m * 3;
       hl_dma16<false>(xs + m * XST + i * 512, rm_bf(a.qkv.a, min(m, R - 1)) + (i * 64 + ln) * 8);
@@ -633,7 +672,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     la_load_tile<W8>(wq, a.qkv.w, a.qkv.w8, w, wave, ln);
     // this wave's A-side DMA: the NWL weight loads (6; W8: 3 -- its exponent load is older) are younger
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWL<W8>) : "memory");
-    if (wave == 0 && RP.cs_tab) {
+    if (ew && RP.cs_tab) {
       const int j = 8 * (w & 7) + 4 * (g4 & 1);
       cs4 = *(const bf16x4*)(RP.cs_tab + (long long)rp * D + j);
       sn4 = *(const bf16x4*)(RP.cs_tab + (long long)rp * D + 64 + j);
@@ -641,7 +680,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   } else if (ot && !(a.variant & 2)) {
     la_load_tile<W8>(wo, a.ow, a.ow8, w - O0, wave, ln);
   }
-  if (threadIdx.x < 2 * RMAX) pre[threadIdx.x + 1] = nunit;
+  if (threadIdx.x < 2 * ROWS) pre[threadIdx.x + 1] = nunit;
   if constexpr (KVQ != 0) {
     if (threadIdx.x < RMAX) {
       tslot[threadIdx.x] = ts;
@@ -651,7 +690,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   __syncthreads();
   if (threadIdx.x == 0) {
     pre[0] = 0;
-    for (int p = 1; p <= 2 * RMAX; ++p) pre[p] += pre[p - 1];
+    for (int p = 1; p <= 2 * ROWS; ++p) pre[p] += pre[p - 1];
   }
   if constexpr (KVQ != 0) {   // (read in phase 2, after the barriers below)
     if (threadIdx.x < RMAX) {
@@ -662,7 +701,7 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   }
   la_stamp(a, 1);
   if (qt) {
-    const int mr = (a.variant & 1) ? R : RMAX;   // (rows >= R of the MFMA are never stored)
+    const int mr = (a.variant & 1) ? R : ROWS;   // (rows >= R of the MFMA are never stored)
     for (int m = wave; m < mr; m += NW) {   // inverse RMS in k_rmsnorm's order
       float ss = 0.f;
       for (int c = ln; c < H / 8; c += 64) {
@@ -676,9 +715,9 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
     __syncthreads();
     hl_rows_norm<H, true, false>(xs, XST, mr, nw_s, nullptr, nullptr, 0, inv_s, hl_vopaque((int)threadIdx.x), NT);
     __syncthreads();
-    la_tile_mfma<W8>(wq, W8 ? w8_scale(hl_vopaque(ex)) : 0.f, xs, red, wave, lane);
+    la_tile_mfma<W8, MT>(wq, W8 ? w8_scale(hl_vopaque(ex)) : 0.f, xs, red, wave, lane);
     __syncthreads();
-    if (wave == 0) la_rope_append<KVQ>(a, red, w, lane, R, rp, rs, rb4, cs4, sn4);
+    if (ew) la_rope_append<KVQ>(a, red + et * (NW * 256), w, lane, 16 * et, R, rp, rs, rb4, cs4, sn4);
   }
   if (!la_wait(a, g0, 1, ok_s, w)) return;
   if (ot && (a.variant & 2)) la_load_tile<W8>(wo, a.ow, a.ow8, w - O0, wave, ln);
@@ -697,23 +736,24 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   if (!la_wait(a, g0, 3, ok_s, w) || !ot) return;
 
   // ================= phase 4: o_proj tile w - O0 over the attention rows + residual
-  for (int q = wave; q < ((a.variant & 1) ? R * 3 : RMAX * 3); q += NW) {
+  for (int q = wave; q < ((a.variant & 1) ? R * 3 : ROWS * 3); q += NW) {
     const int m = q / 3, i = q - m * 3;
     hl_dma16<true>(xs + m * XST + i * 512, a.att + (long long)min(m, R - 1) * H + (i * 64 + ln) * 8);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  la_tile_mfma<W8>(wo, W8 ? w8_scale(hl_vopaque(ex)) : 0.f, xs, red, wave, lane);
+  la_tile_mfma<W8, MT>(wo, W8 ? w8_scale(hl_vopaque(ex)) : 0.f, xs, red, wave, lane);
   __syncthreads();
-  if (wave == 0 && r16 < R) {   // EPI_RES: out = bf16(res + bf16(acc)), row m = lane & 15
-    const int m = r16, n = 16 * (w - O0) + 4 * g4;
+  if (ew && em < R) {   // EPI_RES: out = bf16(res + bf16(acc)), row m = 16 et + (lane & 15)
+    const int m = em, n = 16 * (w - O0) + 4 * g4;
+    const float* redt = red + et * (NW * 256);
     const bf16x4 rv = (a.variant & 4) ? rv_pre : *(const bf16x4*)(rm_bf(a.res, m) + n);
     bf16x4 o;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       float s = 0.f;
 #pragma unroll
-      for (int wv = 0; wv < NW; ++wv) s += red[wv * 256 + lane * 4 + i];
+      for (int wv = 0; wv < NW; ++wv) s += redt[wv * 256 + lane * 4 + i];
       o[i] = tobf(bf(rv[i]) + rb(s));
     }
     *(bf16x4*)(rm_bfw(a.out, m) + n) = o;
@@ -721,51 +761,67 @@ __global__ void __launch_bounds__(la::NT) k_lm_attn(LmAttnArgs a) {
   la_stamp(a, 8);
 }
 
-// ---- host side: the seven forms, one table.  A form is (W8, KVQ, LONG); LONG exactly when the pass is
-// planned past LA_MAX_KEYS.  KVQ = 2 (the diagnostic) is built for bf16 weights only, and the KVQ forms
-// read their own cache formats only in the short step: those five combinations do not exist.
+// ---- host side: the eleven forms, one table.  A form is (W8, KVQ, LONG, MT); LONG exactly when the pass is
+// planned past LA_MAX_KEYS, MT = 2 exactly when the pass has more than 16 rows.  KVQ = 2 (the diagnostic)
+// is built for bf16 weights only, the KVQ forms read their own cache formats only in the short step, and
+// no KVQ form is built at MT = 2 (their tables and staged rows are the 16-row class's): an FP8-KV engine
+// keeps its launches above 16 rows.
 struct LaForm {
   bool w8;
   int kvq;
   bool lng;
+  int mt;
 };
 struct LaKernel {
   LaForm form;
   void (*kernel)(LmAttnArgs);
   bool (*resident)();   // persist_resident_kernel of `kernel`, queried on first use
+  int lds;              // the row class's carve-up (la::Lds<MT>::TOTAL)
 };
-template <bool W8, int KVQ, bool LONG>
+template <bool W8, int KVQ, bool LONG, int MT>
 static bool la_resident() {
-  static const bool ok = persist_resident_kernel((const void*)k_lm_attn<W8, KVQ, LONG>, la::NT, la::TOTAL, la::GRID);
+  static const bool ok =
+      persist_resident_kernel((const void*)k_lm_attn<W8, KVQ, LONG, MT>, la::NT, la::Lds<MT>::TOTAL, la::GRID);
   return ok;
 }
-template <bool W8, int KVQ, bool LONG>
+template <bool W8, int KVQ, bool LONG, int MT = 1>
 constexpr LaKernel la_kernel() {
-  return {{W8, KVQ, LONG}, k_lm_attn<W8, KVQ, LONG>, la_resident<W8, KVQ, LONG>};
+  return {{W8, KVQ, LONG, MT}, k_lm_attn<W8, KVQ, LONG, MT>, la_resident<W8, KVQ, LONG, MT>, la::Lds<MT>::TOTAL};
 }
-static const LaKernel LA_KERNELS[] = {la_kernel<false, 0, false>(), la_kernel<true, 0, false>(), la_kernel<false, 1, false>(),
-                                      la_kernel<true, 1, false>(),  la_kernel<false, 2, false>(), la_kernel<false, 0, true>(),
-                                      la_kernel<true, 0, true>()};
-// the form of a pass of `keys` keys, or nullptr: no such form
-static const LaKernel* la_form(bool w8, int kvq, int keys) {
-  if (keys < 1 || keys > LA_LONG_MAX_KEYS) return nullptr;
-  const LaForm f{w8, kvq, keys > LA_MAX_KEYS};
+static const LaKernel LA_KERNELS[] = {la_kernel<false, 0, false>(),    la_kernel<true, 0, false>(),    la_kernel<false, 1, false>(),
+                                      la_kernel<true, 1, false>(),     la_kernel<false, 2, false>(),   la_kernel<false, 0, true>(),
+                                      la_kernel<true, 0, true>(),      la_kernel<false, 0, false, 2>(), la_kernel<true, 0, false, 2>(),
+                                      la_kernel<false, 0, true, 2>(),  la_kernel<true, 0, true, 2>()};
+// the form of a pass of `rows` rows and `keys` keys, or nullptr: no such form
+static const LaKernel* la_form(bool w8, int kvq, int keys, int rows) {
+  if (keys < 1 || keys > LA_LONG_MAX_KEYS || rows < 1 || rows > 16 * la::MTMAX) return nullptr;
+  const LaForm f{w8, kvq, keys > LA_MAX_KEYS, rows > la::RMAX ? 2 : 1};
   for (const LaKernel& e : LA_KERNELS)
-    if (e.form.w8 == f.w8 && e.form.kvq == f.kvq && e.form.lng == f.lng) return &e;
+    if (e.form.w8 == f.w8 && e.form.kvq == f.kvq && e.form.lng == f.lng && e.form.mt == f.mt) return &e;
   return nullptr;
 }
-extern "C" int vv_diag_lm_attn_form(int w8, int kvq, int keys, int* out) {
-  const LaKernel* e = out && (w8 == 0 || w8 == 1) ? la_form(w8 != 0, kvq, keys) : nullptr;
+extern "C" int vv_diag_lm_attn_form_rows(int w8, int kvq, int keys, int rows, int* out) {
+  const LaKernel* e = out && (w8 == 0 || w8 == 1) ? la_form(w8 != 0, kvq, keys, rows) : nullptr;
   if (!e) return 1;
   out[0] = e->form.w8;
   out[1] = e->form.kvq;
   out[2] = e->form.lng;
+  out[3] = e->form.mt;
+  return 0;
+}
+// (the table of passes of <= 16 rows: out[0..2])
+extern "C" int vv_diag_lm_attn_form(int w8, int kvq, int keys, int* out) {
+  int f[4];
+  if (!out || vv_diag_lm_attn_form_rows(w8, kvq, keys, la::RMAX, f)) return 1;
+  out[0] = f[0];
+  out[1] = f[1];
+  out[2] = f[2];
   return 0;
 }
 
 bool lm_attn_fits(bool w8, int kvq, int H, int nh, int nkv, int d, int R, int keys) {
-  if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D || R < 1 || R > la::RMAX) return false;
-  const LaKernel* e = la_form(w8, kvq, keys);
+  if (H != la::H || nh != la::NH || nkv != la::NKV || d != la::D) return false;
+  const LaKernel* e = la_form(w8, kvq, keys, R);
   return e && e->resident();
 }
 
@@ -797,6 +853,7 @@ int launch_lm_attn(const LmAttnArgs& a, int keys, hipStream_t st) {
   if (!lm_attn_fits(w8, kvq, la::H, la::NH, la::NKV, la::D, a.R, keys) || a.qkv.M != a.R || a.qkv.N != la::NQKV ||
       a.qkv.K != la::H || !a.qkv.epi.bias || !a.part || !a.att || !a.sync || !a.err)
     return 3;
-  hipLaunchKernelGGL(la_form(w8, kvq, keys)->kernel, dim3(la::GRID), dim3(la::NT), la::TOTAL, st, a);
+  const LaKernel* e = la_form(w8, kvq, keys, a.R);
+  hipLaunchKernelGGL(e->kernel, dim3(la::GRID), dim3(la::NT), e->lds, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

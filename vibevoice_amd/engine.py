@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
+from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_max_rows, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
                       pack)
 
 _VALID_IDS_DEFAULT = None
@@ -78,7 +78,7 @@ class Engine:
     def __init__(self, cfg: VibeVoiceConfig, state_dict, device="cuda", max_batch=1, max_ctx=4096,
                  valid_ids=None, tp_rank=0, tp_size=1, tp_unique_id=None, packed=None, tp_head=False,
                  persistent=True, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False,
-                 lm_attn_max_keys=None):
+                 lm_attn_max_keys=None, lm_attn_max_rows=None):
         """tp_size > 1: rank tp_rank's shard of the LM; tp_unique_id (bytes of
         vv_tp_unique_id, shared by the group) creates its RCCL communicator, None
         leaves it for a single-process group (lm_forward_group).
@@ -109,8 +109,15 @@ class Engine:
         (vv_set_lm_attn_max_keys; rows of at most 4,096 keys compute the same bits; bf16 KV --
         an FP8-KV engine keeps its own launches past 4,096 keys).  tp_size 1 only.  Measured
         at B = 1: no context up to 65,536 keys at which the three
-        launches win; at 16 full-length rows they are 3 us per layer ahead near 8K keys."""
+        launches win; at 16 full-length rows they are 3 us per layer ahead near 8K keys.
+        lm_attn_max_rows: None = decode passes of more than 16 rows (B > 8) run the q|k|v,
+        attention and o_proj launches; an int in [16, 32] runs passes of up to that many rows
+        in the one-launch kernel's second row class (vv_set_lm_attn_max_rows; every row computes
+        the bits it computes in a pass of at most 16 rows; bf16 KV -- an FP8-KV engine keeps
+        its launches above 16 rows).  tp_size 1 only.  Combines with lm_attn_max_keys and
+        lm_attn_w8."""
         self.lm_attn_max_keys = check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
+        self.lm_attn_max_rows = check_lm_attn_max_rows(lm_attn_max_rows, tp_size)
         persistent = normalize_persistent(persistent)
         check_weight_dtype(weight_dtype, tp_size)
         check_kv_dtype(kv_dtype, tp_size)
@@ -160,6 +167,8 @@ class Engine:
                 _lib.check(L.vv_set_lm_attn_kv8(h, 1), "set_lm_attn_kv8")
             if self.lm_attn_max_keys is not None:
                 _lib.check(L.vv_set_lm_attn_max_keys(h, self.lm_attn_max_keys), "set_lm_attn_max_keys")
+            if self.lm_attn_max_rows is not None:
+                _lib.check(L.vv_set_lm_attn_max_rows(h, self.lm_attn_max_rows), "set_lm_attn_max_rows")
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")

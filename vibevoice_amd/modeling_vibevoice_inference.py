@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .engine import Engine
-from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
+from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_max_rows, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
 
 
 @dataclass
@@ -174,7 +174,7 @@ class VibeVoiceTokenConstraintProcessor:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VibeVoiceConfig, state_dict, device="cuda", attn_implementation="hip",
                  max_batch=8, max_ctx=8192, tp_group=None, tp_head=None, persistent=True, weight_dtype=None,
-                 kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False, lm_attn_max_keys=None):
+                 kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False, lm_attn_max_keys=None, lm_attn_max_rows=None):
         """tp_group: a torch.distributed process group whose ranks (one per GPU)
         tensor-parallel-shard the Qwen2 backbone over RCCL; every
         rank then runs generate() on the same inputs (SPMD) and gets the same
@@ -206,10 +206,18 @@ class VibeVoiceForConditionalGenerationInference:
         past 4,096 keys keep their launches).  Measured (DESIGN.md §3 "k_lm_attn past 4,096
         keys"): at B = 1 the default max_ctx=8192 steps in 2.46 ms with it against 2.62
         without, and no context up to 65,536 keys favours the three launches; at B = 8 with
-        every row near 8K keys the three launches are about 3 us per layer ahead."""
+        every row near 8K keys the three launches are about 3 us per layer ahead.
+        lm_attn_max_rows: None (the default) keeps the one-launch LM attention kernel to
+        decode passes of at most 16 rows (B <= 8); an int in [16, 32] runs the passes of
+        9 .. 16 dialogues (up to that many rows) in the kernel's second row class (every row
+        computes the bits it computes in a pass of at most 16 rows; no tensor-parallel group,
+        else ValueError; bf16 KV -- with kv_dtype="fp8_e4m3" passes above 16 rows keep their
+        launches).  Measured: DESIGN.md §3 "k_lm_attn at 17 to 32 rows"."""
         max_ctx = min(max_ctx, config.decoder_config.max_position_embeddings)
         check_lm_attn_max_keys(lm_attn_max_keys, max_ctx)
         self.lm_attn_max_keys = lm_attn_max_keys
+        check_lm_attn_max_rows(lm_attn_max_rows)
+        self.lm_attn_max_rows = lm_attn_max_rows
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
         check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
@@ -232,6 +240,7 @@ class VibeVoiceForConditionalGenerationInference:
             check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
             check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size, lm_attn_kv8=lm_attn_kv8)
             check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
+            check_lm_attn_max_rows(lm_attn_max_rows, tp_size)
             if tp_size > 1:
                 box = [Engine.tp_unique_id() if tp_rank == 0 else None]
                 dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
@@ -245,7 +254,8 @@ class VibeVoiceForConditionalGenerationInference:
                              **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
                              **({"lm_attn_w8": True} if lm_attn_w8 else {}),
                              **({"lm_attn_kv8": True} if lm_attn_kv8 else {}),
-                             **({} if lm_attn_max_keys is None else {"lm_attn_max_keys": lm_attn_max_keys}))
+                             **({} if lm_attn_max_keys is None else {"lm_attn_max_keys": lm_attn_max_keys}),
+                             **({} if lm_attn_max_rows is None else {"lm_attn_max_rows": lm_attn_max_rows}))
         self.ddpm_inference_steps = config.diffusion_head_config.ddpm_num_inference_steps
         self.model = _ModelView(self)
         self.use_graphs = True          # capture the steady-state loop body into hipGraphs
@@ -294,7 +304,7 @@ class VibeVoiceForConditionalGenerationInference:
     @classmethod
     def from_pretrained(cls, path, torch_dtype=torch.bfloat16, device_map="cuda", attn_implementation="hip",
                         synthetic_seed=0, weight_dtype=None, kv_dtype=None, lm_attn_w8=False, lm_attn_kv8=False,
-                        lm_attn_max_keys=None, **kw):
+                        lm_attn_max_keys=None, lm_attn_max_rows=None, **kw):
         """`path`: a checkpoint dir (config.json + *.safetensors), or
         "synthetic:1.5B" / "synthetic:Large" for seeded random weights at the
         real shapes (no checkpoints are reachable offline).
@@ -310,12 +320,15 @@ class VibeVoiceForConditionalGenerationInference:
         `lm_attn_w8`: True runs the one-launch LM attention kernel on FP8 weights.
         `lm_attn_kv8`: True runs the one-launch LM attention kernel on the FP8 KV cache.
         `lm_attn_max_keys`: None, or an int in [4096, max_ctx]: decode passes planned up to
-        that many keys run the one-launch LM attention kernel (its long form past 4,096)."""
+        that many keys run the one-launch LM attention kernel (its long form past 4,096).
+        `lm_attn_max_rows`: None, or an int in [16, 32]: decode passes of up to that many rows
+        (B up to half of it) run the one-launch LM attention kernel."""
         check_weight_dtype(weight_dtype)
         check_kv_dtype(kv_dtype)
         check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
         check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
         check_lm_attn_max_keys(lm_attn_max_keys, 1 << 30)   # (the type; the constructor checks the range against its max_ctx)
+        check_lm_attn_max_rows(lm_attn_max_rows)
         resolve_dtype(torch_dtype)
         dev = resolve_device(device_map)
         if str(path).startswith("synthetic:"):
@@ -326,7 +339,7 @@ class VibeVoiceForConditionalGenerationInference:
             sd = load_state_dict(path, cfg)
         return cls(cfg, sd, dev, attn_implementation=attn_implementation, weight_dtype=weight_dtype,
                    kv_dtype=kv_dtype, lm_attn_w8=lm_attn_w8, lm_attn_kv8=lm_attn_kv8,
-                   lm_attn_max_keys=lm_attn_max_keys, **kw)
+                   lm_attn_max_keys=lm_attn_max_keys, lm_attn_max_rows=lm_attn_max_rows, **kw)
 
     @classmethod
     def _from_config(cls, config, torch_dtype=None, device_map="cuda", attn_implementation="hip", seed=0,

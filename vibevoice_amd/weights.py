@@ -266,6 +266,26 @@ def check_lm_attn_max_keys(lm_attn_max_keys, max_ctx=LM_ATTN_KEYS, tp_size=1):
     return lm_attn_max_keys
 
 
+LM_ATTN_ROWS, LM_ATTN_MAX_ROWS = 16, 32   # the kernel's two row classes (kernels.h LA_ROWS / LA_MAX_ROWS)
+
+
+def check_lm_attn_max_rows(lm_attn_max_rows, tp_size=1):
+    """Validate `lm_attn_max_rows`: the most rows of a decode pass (2 B: the conditional and
+    CFG rows of B dialogues) that runs the one-launch LM attention kernel
+    (vv_set_lm_attn_max_rows).  None = the default (16: passes of more rows run the q|k|v,
+    attention and o_proj launches); an int in [16, 32] lets passes of up to that many rows
+    run the kernel's second row class.  tp_size 1 only."""
+    if lm_attn_max_rows is None:
+        return None
+    if isinstance(lm_attn_max_rows, bool) or not isinstance(lm_attn_max_rows, int):
+        raise ValueError(f"lm_attn_max_rows={lm_attn_max_rows!r}: expected None or an int")
+    if tp_size > 1:
+        raise ValueError(f"lm_attn_max_rows is not supported with tensor parallelism (tp_size={tp_size})")
+    if not LM_ATTN_ROWS <= lm_attn_max_rows <= LM_ATTN_MAX_ROWS:
+        raise ValueError(f"lm_attn_max_rows={lm_attn_max_rows} is outside [{LM_ATTN_ROWS}, {LM_ATTN_MAX_ROWS}]")
+    return lm_attn_max_rows
+
+
 def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1, *, lm_attn_kv8=False):
     """The per-engine option that runs the one-launch LM attention kernel on FP8
     weights (vv_set_lm_attn_w8): it needs FP8 weights (`weight_dtype` is the
