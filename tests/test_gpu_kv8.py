@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import kv8_ref
+from attn_ref import head_errs, worst
 from gpu_util import rel_err
 from oracle import lm as olm
 from tiny import tiny_config
@@ -189,6 +190,9 @@ def _check_attention(attn_pair, slots_h, pos_h, form, tag):
     e = rel_err(o8.float().cpu(), ref)
     print(f"{tag}: FP8-cache attention vs fp32 torch over the dequantised rows: rel L2 {e:.3e}")
     assert e < 1e-2, (tag, e)                                                     # test 3: tests/test_gpu_lm.py's bound
+    eh, i, h = worst(head_errs(o8.float().cpu(), ref.reshape(len(pos_h), nh, 128)))
+    print(f"{tag}: worst (row, head) rel L2 {eh:.3e} at row {i} head {h}")
+    assert eh < 1e-2, (tag, eh, i, h)                                             # ... per (row, head), not pooled
 
 
 KEYS = [1, 31, 32, 33, 97, 255]

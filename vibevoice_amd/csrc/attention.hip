@@ -903,6 +903,7 @@ int launch_attn(AttnArgs a, hipStream_t st) {
   if (f8 && (!a.kv8.v || !a.kv8.ek || !a.kv8.ev || a.kv.s_layer % 128 || a.kv.s_slot % 128 || a.kv.s_head % 128 ||
              a.kv.max_ctx % 64))
     return 1;
+  if (a.prefill && a.kv.max_ctx % (32 * PF_SUB)) return 1;   // k_attn_pf issues whole 64-key stages, past nk too
   if (a.prefill) return f8 ? launch_attn_pf<unsigned char>(a, st) : launch_attn_pf<bf16>(a, st);
   if (a.chunk % ATT_KC || a.nsplit > ATT_SPLITS_MAX) return 1;
   if ((a.nsplit > 1 || a.defer) && (!a.part_o || !a.part_ml || !a.counters)) return 1;

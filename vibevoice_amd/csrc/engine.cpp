@@ -2839,6 +2839,8 @@ int vv_attention_bf16(int nq, int nh, int nkv, const void* q, const void* k_cach
   int chunk = 0;
   // the slot count is unknown here: auto keeps k_attn (vv_attn_prefill(1) forces k_attn_pf)
   at.prefill = attn_use_prefill(nq, nq) ? 1 : 0;
+  if (at.prefill && s_head % (128 * 64))
+    FAIL("vv_attention_bf16: the prefill kernel stages 64 keys at a time (s_head % 8192 != 0)");
   at.nsplit = at.prefill ? 1 : attn_plan(nq, nkv, max_pos_p1, &chunk);
   if (at.nsplit > 1) {
     if ((size_t)nq * nkv > 65536) FAIL("attention split tickets exhausted");
