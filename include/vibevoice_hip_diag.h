@@ -263,6 +263,17 @@ int vv_diag_lm_attn_form(int w8, int kvq, int keys, int* out);
  * weights, short or long.  Nonzero: kvq != 0 above 16 rows, rows outside 1 .. 32,
  * a null out. */
 int vv_diag_lm_attn_form_rows(int w8, int kvq, int keys, int rows, int* out);
+/* Diagnostic: the attention half's route for a pass of `rows` rows planned for
+ * `keys` keys, as a function of plain values -- how qkv_w / o_w are bound
+ * (attn_form: 0 all bf16, 1 all FP8 pairs, 2 a mix), the KV format (0 / 1), the
+ * four per-context options (vv_set_lm_attn_w8 / _kv8 / _max_keys / _max_rows),
+ * max_ctx, vv_lm_attn_kvround and whether the context has a staging cache.
+ * out[0..2] = (one, w8, kvq): one = 0 is the q|k|v, attention and o_proj
+ * launches; w8 / kvq name the k_lm_attn form asked for (vv_diag_lm_attn_form_rows
+ * says whether it is built).  The function every pass and vv_finalize evaluate;
+ * residency, buffers, switches and tensor parallelism are the pass plan's. */
+int vv_diag_lm_attn_route(int attn_form, int kv_dtype, int w8, int kv8, int max_keys, int max_rows, int max_ctx,
+                          int kvround, int staged, int rows, int keys, int* out);
 /* Diagnostic (bench.py): `reps` passes over the LM layers' attention halves alone
  * on ntok decode rows (embeds [ntok][H] as layer 0's input, slots / positions as
  * for vv_lm_forward). */

@@ -415,3 +415,86 @@ def test_lm_attn_one_launch_limits():
     finally:
         L_.vv_lm_attn(1)
     assert L_.vv_lm_attn_active(eng.h, 2, 100) == 1
+
+
+def test_lm_plan_at_the_class_edges():
+    """One engine with both options (lm_attn_max_keys = 8192, lm_attn_max_rows = 32), one decode pass on each
+    side of every class edge of the pass plan (engine.cpp lm_plan): 2 rows (k_lm_ffn), 16 rows (k_lm_ffn16),
+    17 rows (k_lm_attn's second row class; the MLP as chunks of 16 + 1 rows) and 32 rows planned at 4,097
+    keys (the long form; chunks of 16 + 16).  Per pass: vv_lm_attn_active reports the one launch;
+    vv_lm_ffn_active of each MLP chunk's row count matches the launches the pass made, counted from the
+    kernels' own generation words (one grid wait, 8 bumps, per k_lm_ffn / k_lm_ffn16 launch); the hidden rows
+    of a repeat run are the same bits.  Passes of at most 16 rows against the same pass with vv_lm_attn(0)
+    and vv_lm_ffn(0): rel < 2e-2, cosine > 0.999 -- the relation the tests above establish between the two
+    routes (their sums run in another order, so no test asserts equal bits there; the count of differing
+    values is printed: 420 of 3,072 at 2 rows, 1 of 24,576 at 16 rows).  17 and 32 rows against the rows' passes of at most 16 rows, bit for bit, as
+    tests/test_gpu_lm_attn_rows.py test_rows_compute_the_16_row_kernels_bits compares them."""
+    import ctypes
+    import gc
+    from sync_counters import LINES, N_WORDS
+    from vibevoice_amd import _lib
+    gc.collect()
+    L_ = _lib.lib()
+    layers = 2
+    cfg = tiny_config(hidden=1536, layers=layers, heads=12, kv_heads=2, inter=8960)
+    sd = synthetic_state_dict(cfg, seed=17, device="cpu", mode="test", with_acoustic_encoder=False)
+    eng = Engine(cfg, sd, dev, max_batch=16, max_ctx=8192, valid_ids=[151643, 151652, 151653, 151654],
+                 lm_attn_max_keys=8192, lm_attn_max_rows=32)
+    kv_synthetic(eng, torch.arange(32).to(**I32), 0, 4097, seed=5)
+    g = torch.Generator().manual_seed(19)
+
+    def launches():   # (k_lm_ffn, k_lm_ffn16, k_lm_attn's waits) so far: the LM buffer's generation words / 8
+        words = (ctypes.c_uint * N_WORDS)()
+        _lib.check(L_.vv_diag_sync_words(eng.h, words, N_WORDS), "sync_words")
+        lm = list(words[2 * (LINES + 1):3 * (LINES + 1)])
+        assert lm[11] % 8 == 0 and lm[12] % 8 == 0 and lm[15] % 8 == 0, lm
+        return torch.tensor([lm[11] // 8, lm[12] // 8, lm[15] // 8])
+
+    def run(x, a, b, pos, keys):
+        assert L_.vv_lm_attn_active(eng.h, b - a, keys) == (1 if on else 0), (a, b, keys)
+        ar = torch.arange(b - a).to(**I32)
+        h, _ = eng.lm_forward(x[a:b].contiguous(), torch.arange(a, b).to(**I32), pos[a:b].contiguous(), ar,
+                              max_pos=keys - 1)
+        torch.cuda.synchronize()
+        return h.clone()
+
+    on = True
+    try:
+        for rows, keys in ((2, 64), (16, 64), (17, 64), (32, 4097)):
+            x = torch.randn(rows, 1536, generator=g).bfloat16().to(dev)
+            pos = torch.tensor([keys - 1] + [(11 * r) % 61 for r in range(1, rows)]).to(**I32)   # ragged; row 0 the longest
+            chunks = [(a, min(a + 16, rows)) for a in range(0, rows, 16)]
+            active = {b - a: L_.vv_lm_ffn_active(eng.h, b - a) for a, b in chunks}
+            n0 = launches()
+            h = run(x, 0, rows, pos, keys)
+            n = launches() - n0
+            want = [layers * sum(active[b - a] for a, b in chunks if b - a <= 2),
+                    layers * sum(active[b - a] for a, b in chunks if b - a > 2)]
+            print(f"rows {rows} keys {keys}: vv_lm_ffn_active {active}; launches k_lm_ffn {int(n[0])} k_lm_ffn16 "
+                  f"{int(n[1])} (want {want}), k_lm_attn waits {int(n[2])}")
+            assert n[:2].tolist() == want and n[2] > 0 and all(v == 1 for v in active.values())
+            assert torch.equal(h, run(x, 0, rows, pos, keys))
+            if rows <= 16:
+                on = False
+                L_.vv_lm_attn(0)
+                L_.vv_lm_ffn(0)
+                assert L_.vv_lm_ffn_active(eng.h, rows) == 0
+                n0 = launches()
+                off = run(x, 0, rows, pos, keys)
+                assert (launches() - n0).tolist() == [0, 0, 0]
+                L_.vv_lm_attn(1)
+                L_.vv_lm_ffn(1)
+                on = True
+                print(f"rows {rows}: {int((h != off).sum())} of {h.numel()} hidden values differ from the launches' "
+                      f"(rel {rel_err(h, off):.3e}, cos {cos(h, off):.6f})")
+                assert rel_err(h, off) < 2e-2 and cos(h, off) > 0.999
+            else:
+                parts = torch.cat([run(x, a, b, pos, keys) for a, b in chunks])
+                print(f"rows {rows}: {int((h != parts).sum())} of {h.numel()} hidden values differ from the passes of <= 16 rows'")
+                assert torch.equal(h, parts)
+    finally:
+        L_.vv_lm_attn(1)
+        L_.vv_lm_ffn(1)
+    eng.check_sync()
+    assert_counters_consistent(eng)
+    eng.close()

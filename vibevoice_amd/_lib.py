@@ -111,6 +111,7 @@ EXPORTS = [
     ("vv_diag_lm_attn_plan", I, [I, ctypes.POINTER(I)]),
     ("vv_diag_lm_attn_form", I, [I, I, I, ctypes.POINTER(I)]),
     ("vv_diag_lm_attn_form_rows", I, [I, I, I, I, ctypes.POINTER(I)]),
+    ("vv_diag_lm_attn_route", I, [I] * 11 + [ctypes.POINTER(I)]),
     ("vv_diag_attn_row_splits", I, [I, I, I, I, ctypes.POINTER(I)]),
     ("vv_lm_attn_stamps", I, [P]),
     ("vv_lm_attn_replay", I, [P, I, P, P, P, I, I, P]),

@@ -1036,9 +1036,17 @@ int vv_bind_weight(vv_ctx* c, const char* name, const void* p, const int64_t* sh
   return 0;
 }
 
+// What every option setter refuses first: a null context, a call after vv_finalize (`why`: what is settled by
+// then) and, with no_tp, a tensor-parallel engine.
+static int option_guard(vv_ctx* c, const std::string& fn, const char* why, bool no_tp) {
+  if (!c) FAIL(fn + ": null context");
+  if (c->finalized) FAIL(fn + " after vv_finalize: " + why);
+  if (no_tp && (c->tp_size > 1 || c->comm)) FAIL(fn + " is not supported on a tensor-parallel engine");
+  return 0;
+}
+static const char* const LA_CHOSEN = "the attention half's kernels are already chosen";
 int vv_set_kv_dtype(vv_ctx* c, int dtype) {
-  if (!c) FAIL("vv_set_kv_dtype: null context");
-  if (c->finalized) FAIL("vv_set_kv_dtype after vv_finalize: the KV cache is already allocated");
+  CHK(option_guard(c, "vv_set_kv_dtype", "the KV cache is already allocated", false));
   if (dtype != 0 && dtype != 1)
     FAIL("vv_set_kv_dtype: unsupported dtype " + std::to_string(dtype) + " (0 = bf16, 1 = fp8 e4m3)");
   if (dtype && (c->tp_size > 1 || c->comm)) FAIL("an FP8 KV cache is not supported on a tensor-parallel engine");
@@ -1046,26 +1054,19 @@ int vv_set_kv_dtype(vv_ctx* c, int dtype) {
   return 0;
 }
 int vv_kv_dtype(vv_ctx* c) { return c ? c->kv_dtype : 0; }
-int vv_set_lm_attn_w8(vv_ctx* c, int on) {
-  if (on != 0 && on != 1) FAIL("vv_set_lm_attn_w8: unsupported value " + std::to_string(on) + " (0 = off, 1 = on)");
-  if (!c) FAIL("vv_set_lm_attn_w8: null context");
-  if (c->finalized) FAIL("vv_set_lm_attn_w8 after vv_finalize: the attention half's kernels are already chosen");
-  c->lm_attn_w8 = on;
+// (the two on / off options; they leave refusing a tensor-parallel engine to their callers)
+static int set_lm_attn_flag(vv_ctx* c, const std::string& fn, int on, int vv_ctx::*opt) {
+  if (on != 0 && on != 1) FAIL(fn + ": unsupported value " + std::to_string(on) + " (0 = off, 1 = on)");
+  CHK(option_guard(c, fn, LA_CHOSEN, false));
+  c->*opt = on;
   return 0;
 }
+int vv_set_lm_attn_w8(vv_ctx* c, int on) { return set_lm_attn_flag(c, "vv_set_lm_attn_w8", on, &vv_ctx::lm_attn_w8); }
 int vv_lm_attn_w8(vv_ctx* c) { return c ? c->lm_attn_w8 : 0; }
-int vv_set_lm_attn_kv8(vv_ctx* c, int on) {
-  if (on != 0 && on != 1) FAIL("vv_set_lm_attn_kv8: unsupported value " + std::to_string(on) + " (0 = off, 1 = on)");
-  if (!c) FAIL("vv_set_lm_attn_kv8: null context");
-  if (c->finalized) FAIL("vv_set_lm_attn_kv8 after vv_finalize: the attention half's kernels are already chosen");
-  c->lm_attn_kv8 = on;
-  return 0;
-}
+int vv_set_lm_attn_kv8(vv_ctx* c, int on) { return set_lm_attn_flag(c, "vv_set_lm_attn_kv8", on, &vv_ctx::lm_attn_kv8); }
 int vv_lm_attn_kv8(vv_ctx* c) { return c ? c->lm_attn_kv8 : 0; }
 int vv_set_lm_attn_max_keys(vv_ctx* c, int keys) {
-  if (!c) FAIL("vv_set_lm_attn_max_keys: null context");
-  if (c->finalized) FAIL("vv_set_lm_attn_max_keys after vv_finalize: the attention half's kernels are already chosen");
-  if (c->tp_size > 1 || c->comm) FAIL("vv_set_lm_attn_max_keys is not supported on a tensor-parallel engine");
+  CHK(option_guard(c, "vv_set_lm_attn_max_keys", LA_CHOSEN, true));
   const int hi = std::min(c->cfg.max_ctx, LA_LONG_MAX_KEYS);
   if (keys < LA_MAX_KEYS || keys > hi)
     FAIL("vv_set_lm_attn_max_keys: " + std::to_string(keys) + " is outside [" + std::to_string(LA_MAX_KEYS) + ", " +
@@ -1075,9 +1076,7 @@ int vv_set_lm_attn_max_keys(vv_ctx* c, int keys) {
 }
 int vv_lm_attn_max_keys(vv_ctx* c) { return c ? c->lm_attn_max_keys : 0; }
 int vv_set_lm_attn_max_rows(vv_ctx* c, int rows) {
-  if (!c) FAIL("vv_set_lm_attn_max_rows: null context");
-  if (c->finalized) FAIL("vv_set_lm_attn_max_rows after vv_finalize: the attention half's kernels are already chosen");
-  if (c->tp_size > 1 || c->comm) FAIL("vv_set_lm_attn_max_rows is not supported on a tensor-parallel engine");
+  CHK(option_guard(c, "vv_set_lm_attn_max_rows", LA_CHOSEN, true));
   if (rows < LA_ROWS || rows > LA_MAX_ROWS)
     FAIL("vv_set_lm_attn_max_rows: " + std::to_string(rows) + " is outside [" + std::to_string(LA_ROWS) + ", " +
          std::to_string(LA_MAX_ROWS) + "]");
@@ -1108,24 +1107,39 @@ extern "C" int vv_lm_attn_kvround(int on) {
   g_lm_attn_kvround = on ? 1 : 0;
   return 0;
 }
-// k_lm_attn's form for this context at a pass of `rows` rows planned for `keys` keys, decided here only:
-// `one` = false is the three launches (q|k|v, k_attn, o_proj).  Above LA_ROWS rows: with the context's
-// lm_attn_max_rows, raw rows into a bf16 cache only (no KVQ form is built there).
-// w8: every layer's qkv_w and o_w bound as codes with the context's option on (bf16 throughout: the bf16 form; a mixed binding, or codes without the option: the
-// three launches).  kvq: 0 raw rows into a bf16 cache, 1 the FP8 cache with its option (without it: the
-// three launches + k_kv_quant), 2 the diagnostic round trip.  Which (w8, kvq, keys) are built, and
-// resident, is lm_attn_fits' to say.
-struct LmAttnForm {
-  bool one, w8;
-  int kvq;
-};
-static LmAttnForm lm_attn_form(vv_ctx* c, int keys, int rows) {
-  const bool w8 = c->attn_form == vv_ctx::MLP_W8 && c->lm_attn_w8;
-  const int kvq = c->kv_dtype ? 1 : g_lm_attn_kvround && c->attn_form == vv_ctx::MLP_BF16 && c->stg.k ? 2 : 0;
-  const bool one = (w8 || c->attn_form == vv_ctx::MLP_BF16) && (!c->kv_dtype || c->lm_attn_kv8) &&
-                   keys <= std::min(c->cfg.max_ctx, c->lm_attn_max_keys) &&
-                   (rows <= LA_ROWS || (rows <= c->lm_attn_max_rows && kvq == 0));
+// The attention half's route for a pass of `rows` rows planned for `keys` keys, decided here only and from
+// plain values (LmAttnOpts: how qkv_w / o_w are bound, the KV format, the context's four options, max_ctx,
+// the round-trip switch, whether a staging cache exists).  `one` = false is the three launches (q|k|v,
+// k_attn, o_proj).  w8: every layer's qkv_w and o_w bound as codes with the option on (bf16 throughout: the
+// bf16 form; a mixed binding, or codes without the option: the three launches).  kvq: 0 raw rows into a bf16
+// cache, 1 the FP8 cache with its option (without it: the three launches + k_kv_quant), 2 the diagnostic
+// round trip.  Above LA_ROWS rows: with max_rows, raw rows into a bf16 cache only (no KVQ form is built
+// there).  Which (w8, kvq, keys, rows) are built, and resident, is lm_attn_fits' to say.
+struct LmAttnOpts { int attn_form, kv_dtype, w8, kv8, max_keys, max_rows, max_ctx, kvround, staged; };
+struct LmAttnRoute { bool one, w8; int kvq; };
+static LmAttnRoute lm_attn_route(const LmAttnOpts& o, int rows, int keys) {
+  const bool w8 = o.attn_form == vv_ctx::MLP_W8 && o.w8;
+  const int kvq = o.kv_dtype ? 1 : o.kvround && o.attn_form == vv_ctx::MLP_BF16 && o.staged ? 2 : 0;
+  const bool one = (w8 || o.attn_form == vv_ctx::MLP_BF16) && (!o.kv_dtype || o.kv8) &&
+                   keys <= std::min(o.max_ctx, o.max_keys) && (rows <= LA_ROWS || (rows <= o.max_rows && kvq == 0));
   return {one, w8, kvq};
+}
+// diagnostic: out = {one, w8, kvq} of lm_attn_route (attn_form: 0 bf16, 1 FP8, 2 mixed)
+extern "C" int vv_diag_lm_attn_route(int attn_form, int kv_dtype, int w8, int kv8, int max_keys, int max_rows,
+                                     int max_ctx, int kvround, int staged, int rows, int keys, int* out) {
+  if (!out) return 1;
+  const LmAttnRoute r = lm_attn_route({attn_form, kv_dtype, w8, kv8, max_keys, max_rows, max_ctx, kvround, staged}, rows, keys);
+  const int v[3] = {r.one, r.w8, r.kvq};
+  std::copy(v, v + 3, out);
+  return 0;
+}
+static LmAttnOpts lm_attn_opts(const vv_ctx* c) {
+  return {c->attn_form, c->kv_dtype, c->lm_attn_w8, c->lm_attn_kv8, c->lm_attn_max_keys, c->lm_attn_max_rows,
+          c->cfg.max_ctx, g_lm_attn_kvround.load(), c->stg.k != nullptr};
+}
+static bool lm_attn_route_fits(const vv_ctx* c, const LmAttnRoute& r, int rows, int keys) {
+  const vv_config& k = c->cfg;
+  return r.one && lm_attn_fits(r.w8, r.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, rows, keys);
 }
 
 int vv_finalize(vv_ctx* c) {
@@ -1225,27 +1239,22 @@ int vv_finalize(vv_ctx* c) {
   const bool lf_fits = mlp_one && lm_ffn_fits(mlp_w8, k.hidden, k.intermediate, 2);
   const bool lf16_fits = mlp_one && lm_ffn16_fits(mlp_w8, k.hidden, k.intermediate, 16);
   if (k.max_batch >= 2 && lf16_fits) CHK(c->lf_slab.ensure(48 * 4 * 16 * 32 * sizeof(float)));
-  const int la_keys = std::min(k.max_ctx, c->lm_attn_max_keys), la_rows = std::min(2 * k.max_batch, LA_ROWS);
-  // (the residency of the form this context will run (lm_attn_form): the short form's, and with
-  // lm_attn_max_keys past LA_MAX_KEYS the long form's as well, both queried here: an engine with the option
-  // runs the short form for passes planned at <= LA_MAX_KEYS.  The long form reads a bf16 cache: an FP8-KV
-  // engine keeps k_kv_quant + k_attn past LA_MAX_KEYS.)
-  const int la_short = std::min(la_keys, LA_MAX_KEYS);
-  const LmAttnForm la_f = lm_attn_form(c, la_short, la_rows), la_fl = lm_attn_form(c, la_keys, la_rows);
-  const bool la_fits = la_f.one && lm_attn_fits(la_f.w8, la_f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_short) &&
-                       c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim;
-  if (la_fits && la_keys > LA_MAX_KEYS && la_fl.one)
-    (void)lm_attn_fits(la_fl.w8, la_fl.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_rows, la_keys);
-  // (the rows the context's lm_attn_max_rows allows above LA_ROWS: that row class's forms are queried as
-  // well, and the partials sized for it; an engine whose form is not built there keeps la_rows)
-  int la_top = la_rows;
-  const int la_wide = std::min(2 * k.max_batch, c->lm_attn_max_rows);
-  if (la_fits && la_wide > LA_ROWS && lm_attn_form(c, la_short, la_wide).one &&
-      lm_attn_fits(la_f.w8, la_f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_wide, la_short)) {
-    la_top = la_wide;
-    if (la_keys > LA_MAX_KEYS && lm_attn_form(c, la_keys, la_wide).one)
-      (void)lm_attn_fits(la_fl.w8, la_fl.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, la_wide, la_keys);
-  }
+  // k_lm_attn: the (row class, key class) corners this context can reach, each through a pass's own route and
+  // lm_attn_fits, so every form it may run has its residency queried here, not in a hot call or a graph capture.
+  // The base corner (<= LA_ROWS rows, <= LA_MAX_KEYS keys) decides la_fits; the wider ones count only then, a row
+  // class's long corner only after its short one.  la_top: the most rows admitted; the partials are sized for them.
+  const int la_keys = std::min(k.max_ctx, c->lm_attn_max_keys);
+  const int la_rows[2] = {std::min(2 * k.max_batch, LA_ROWS), std::min(2 * k.max_batch, c->lm_attn_max_rows)};
+  const int la_kcls[2] = {std::min(la_keys, LA_MAX_KEYS), la_keys};
+  const LmAttnOpts la_o = lm_attn_opts(c);
+  int la_top = 0;
+  for (int ri = 0; ri < (la_top && la_rows[1] > LA_ROWS ? 2 : 1); ++ri)
+    for (int ki = 0; ki < (la_keys > LA_MAX_KEYS ? 2 : 1); ++ki) {
+      const bool fits = lm_attn_route_fits(c, lm_attn_route(la_o, la_rows[ri], la_kcls[ki]), la_rows[ri], la_kcls[ki]);
+      if (ki == 0 && !fits) break;
+      if (ki == 0) la_top = la_rows[ri];
+    }
+  const bool la_fits = la_top > 0;
   if (la_fits) CHK(c->la_part.ensure(lm_attn_part_floats(la_top, la_keys) * sizeof(float)));
   CHK(c->cw_sync.ensure(pk::CW_BYTES));
   HIPCHK(hipMemset(c->cw_sync.p, 0, pk::CW_BYTES));
@@ -1435,16 +1444,8 @@ extern "C" int vv_attn_group(int on) {      // 1 = default; n >= 2: at most n sp
   g_attn_group = on == 1 ? 120 : on <= 0 ? 0 : std::min(on, 128);
   return 0;
 }
-struct LmPass {
-  int ntok = 0, nsplit = 1, chunk = 64, prefill = 0, defer = 0, group = 0, ngroups = 0;
-  int maxp = 0;   // keys of the longest row (max position + 1)
-  bf16 *h = nullptr, *q = nullptr, *att = nullptr, *act = nullptr;
-  RowMap in_m, hm;
-  const int *slot = nullptr, *pos = nullptr;
-};
-
 // The decode attention's plan for a pass of ntok rows over max_pos_p1 keys
-// (lm_begin; vv_attn_pass_plan reports it to the CPU tests): prefill kernel or
+// (lm_plan; vv_attn_pass_plan reports it to the CPU tests): prefill kernel or
 // not, key splits, deferred merge (o_proj merges), grouped merge.
 struct AttnPassPlan {
   int prefill = 0, nsplit = 1, chunk = 64, defer = 0, group = 0, ngroups = 0;
@@ -1494,48 +1495,6 @@ extern "C" int vv_attn_pass_plan(int ntok, int lm_slots, int head_dim, int n_kv,
   return 0;
 }
 
-static int lm_begin(vv_ctx* c, LmPass& P, int ntok, const void* embeds, int embed_rows, const int* slot,
-                    const int* pos, int max_pos_p1) {
-  if (!c->finalized) FAIL("vv_lm_forward before vv_finalize");
-  if (max_pos_p1 > c->cfg.max_ctx) FAIL("position beyond max_ctx");
-  const vv_config& k = c->cfg;
-  const int H = k.hidden, d = k.head_dim, I = k.intermediate, nhd = k.n_heads * d;
-  const size_t per = (size_t)H * 3 + c->qkv_n + nhd * 2 + I;
-  if (c->kv_dtype) CHK(kv_stage_ensure(c, (size_t)ntok));
-  if ((size_t)ntok > c->lm_ws_tokens) {
-    // + 16 act rows: a packed act block (vv_norm_pack) rounds the rows up to 16
-    CHK(c->lm_ws.ensure((per * ntok + (size_t)16 * I) * sizeof(bf16) + 256));
-    c->lm_ws_tokens = ntok;
-  }
-  P.ntok = ntok;
-  P.maxp = max_pos_p1;
-  P.h = (bf16*)c->lm_ws.p;
-  bf16* a = P.h + (size_t)ntok * H;
-  bf16* qkv = a + (size_t)ntok * H;
-  P.q = qkv + (size_t)ntok * c->qkv_n;
-  P.att = P.q + (size_t)ntok * nhd;
-  P.act = P.att + (size_t)ntok * nhd;
-  const AttnPassPlan ap = attn_pass_plan(ntok, c->lm_slots, k.head_dim, k.n_kv_heads, max_pos_p1);
-  P.prefill = ap.prefill;
-  P.nsplit = ap.nsplit;
-  P.chunk = ap.chunk;
-  P.defer = ap.defer;
-  P.group = ap.group;
-  P.ngroups = ap.ngroups;
-  if (P.nsplit > 1) {
-    if ((size_t)ntok * k.n_kv_heads * std::max(1, P.ngroups) > 65536) FAIL("attention split tickets exhausted");
-    CHK(c->attn_part.ensure(attn_part_bytes(ntok, k.n_heads, P.nsplit, P.ngroups)));
-  }
-  // token row m reads embeds row m % embed_rows (the negative CFG rows consume the
-  // positive rows' embeddings, :594-596); layer 0's attention residual writes h
-  if (embed_rows <= 0 || embed_rows > ntok) embed_rows = ntok;
-  P.in_m = rowmap(embeds, H, embed_rows, 0);
-  P.hm = rowmap(P.h, H);
-  P.slot = slot;
-  P.pos = pos;
-  return 0;
-}
-
 // residual epilogue of a row-parallel projection: rank 0 adds the residual,
 // the other ranks contribute their partial only (the all-reduce sums them)
 static void tp_residual(vv_ctx* c, GemmArgs& g, const RowMap& res) {
@@ -1560,115 +1519,6 @@ extern "C" int vv_lm_attn_stamps(void* buf) {   // diagnostic: k_lm_attn launche
   g_lm_attn_stamps = (unsigned long long*)buf;
   return 0;
 }
-static bool lm_attn_on(vv_ctx* c, const LmPass& P) {
-  const vv_config& k = c->cfg;
-  const LmAttnForm f = lm_attn_form(c, P.maxp, P.ntok);
-  return f.one && g_lm_attn && c->la_part.p && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm &&
-         c->qkv_n == (k.n_heads + 2 * k.n_kv_heads) * k.head_dim && !P.hm.idx && P.hm.sT == k.hidden &&
-         P.hm.T >= P.ntok && lm_attn_fits(f.w8, f.kvq, k.hidden, k.n_heads, k.n_kv_heads, k.head_dim, P.ntok, P.maxp) &&
-         lm_attn_part_floats(P.ntok, P.maxp) * sizeof(float) <= c->la_part.bytes && persist_on(c);
-}
-extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
-  if (!c || !c->finalized) return 0;
-  LmPass P;
-  P.ntok = ntok;
-  P.maxp = max_pos_p1;
-  P.prefill = attn_use_prefill(ntok, c->lm_slots) ? 1 : 0;
-  P.hm = rowmap(nullptr, c->cfg.hidden);
-  return lm_attn_on(c, P) ? 1 : 0;
-}
-
-// input_layernorm .. o_proj (+ residual on rank 0)
-static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
-  const vv_config& k = c->cfg;
-  const int H = k.hidden, d = k.head_dim, nhd = k.n_heads * d;
-  const LmLayerW& w = c->lmw[l];
-  {
-    // input_layernorm -> q|k|v projection (+bias) -> RoPE -> q / KV cache, one launch
-    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, w.qkv, EPI_ROPE, RowMap{},
-                           w.qkv_b);
-    g.xf = xf_norm(w.in_norm, k.rms_eps);
-    g.rope.nh = k.n_heads;
-    g.rope.nkv = k.n_kv_heads;
-    g.rope.layer = l;
-    g.rope.q_out = P.q;
-    g.rope.slots = P.slot;
-    g.rope.pos = P.pos;
-    g.rope.inv_freq = c->lm.inv_freq;
-    g.rope.cs_tab = g_rope_tab ? (const bf16*)c->rope_tab.p : nullptr;
-    g.rope.kv = c->kv;
-    // (k_lm_attn's KVQ forms stage and quantise inside the launch: the real tables, no prep, no k_kv_quant)
-    const bool one = lm_attn_on(c, P);
-    if (c->kv_dtype && !one) {
-      // FP8 KV: the epilogue appends to the staging cache (token m at slot 0, position m; cos / sin
-      // from the pass's rows of the real positions), k_kv_quant below moves the rows to the cache
-      if (l == 0)
-        KCHK(launch_kv_stage_prep(P.ntok, (int)c->kv_stage_tokens, P.pos, c->kv.max_ctx, (const bf16*)c->rope_tab.p, c->stg_cs, c->stg_slot,
-                                  c->stg_pos, st));
-      g.rope.slots = c->stg_slot;
-      g.rope.pos = c->stg_pos;
-      g.rope.cs_tab = c->stg_cs;
-      g.rope.kv = c->stg;
-    }
-    if (one) {
-      LmAttnArgs a;
-      memset(&a, 0, sizeof(a));
-      a.qkv = g;
-      a.kvq = lm_attn_form(c, P.maxp, P.ntok).kvq;
-      a.stg = c->stg;
-      a.kv8 = c->kv8;
-      a.nw = w.in_norm;
-      a.eps = k.rms_eps;
-      a.scale = 1.0f / sqrtf((float)d);
-      a.R = P.ntok;
-      a.ow = w.o.w;
-      a.ow8 = w.o.w8;     // codes throughout: the launcher picks the W8 form (a.qkv carries q|k|v's)
-      a.owe = w.o.w8e;
-      a.res =l == 0 ? P.in_m : P.hm;
-      a.out = P.hm;
-      a.att = P.att;
-      a.part = (float*)c->la_part.p;
-      a.sync = (unsigned*)c->lf_sync.p;
-      a.err = err_word(c);
-      a.stamps = g_lm_attn_stamps.load();
-      a.variant = 7 ^ (g_lm_attn.load() >> 1);
-      KCHK(launch_lm_attn(a, P.maxp, st));
-      return 0;
-    }
-    CHK(gemm(c, g, st));
-    if (c->kv_dtype)
-      KCHK(launch_kv_quant(c->stg, c->kv, c->kv8, l, k.n_kv_heads, c->lm_slots, P.ntok, P.slot, P.pos, st));
-  }
-  AttnArgs at;
-  memset(&at, 0, sizeof(at));
-  at.kv8 = c->kv8;
-  at.stamps = g_attn_stamps;
-  at.nq = P.ntok;
-  at.nh = k.n_heads;
-  at.nkv = k.n_kv_heads;
-  at.layer = l;
-  at.nsplit = P.nsplit;
-  at.chunk = P.chunk;
-  at.prefill = P.prefill;
-  at.defer = P.defer;
-  at.counters = (unsigned*)c->attn_cnt.p;
-  at.scale = 1.0f / sqrtf((float)d);
-  at.q = P.q;
-  at.out = P.att;
-  at.slots = P.slot;
-  at.pos = P.pos;
-  at.kv = c->kv;
-  at.group = P.group;
-  at.ngroups = P.ngroups;
-  attn_part_carve(at, c->attn_part.p);
-  KCHK(launch_attn(at, st));
-  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), w.o, EPI_RES, P.hm);
-  if (P.defer || P.group) attn_merge_xf(g, at);
-  tp_residual(c, g, l == 0 ? P.in_m : P.hm);
-  CHK(gemm(c, g, st));
-  return 0;
-}
-
 // the LM MLP block in one launch (lm_ffn.hip) at decode with <= 2 rows, unsharded,
 // while the context is the device's only registered one; 0 = two GEMV launches
 static std::atomic<int> g_lm_ffn{1};
@@ -1691,92 +1541,255 @@ extern "C" int vv_lm_ffn_w8(int bits) {
   g_ws_epoch.fetch_add(1);
   return 0;
 }
-static bool lm_ffn_on(vv_ctx* c, const LmPass& P) {
+
+// Which kernels a pass of ntok rows planned for `keys` keys runs (DESIGN.md "How an LM pass picks its kernels"),
+// decided once per pass, not at vv_finalize: persist_on follows the contexts registered at that moment and the
+// diagnostic switches may flip between passes; each is read once here.  The layers' halves decide nothing.
+enum FfnRoute { FFN_GEMMS = 0, FFN_ONE = 1, FFN_ONE16 = 2 };   // the GEMM pair, k_lm_ffn (<= 2 rows), k_lm_ffn16 (3..16)
+struct LmPlan {
+  AttnPassPlan attn;               // k_attn's launch plan (the three launches; `prefill` bars every one-launch kernel)
+  LmAttnRoute la{false, false, 0}; // la.one: the attention half is one k_lm_attn launch, in the form (la.w8, la.kvq)
+  int la_variant = 0;              // LmAttnArgs::variant (vv_lm_attn's A/B bits)
+  bool stage_kv = false;           // three launches on an FP8-KV context: staging prep at layer 0, k_kv_quant per layer
+  // the MLP half runs in chunks of mlp_rows rows: the whole pass, or LA_ROWS where the attention half took
+  // k_lm_attn's second row class (the GEMMs of 17 .. 32 rows sum K in another order: every row keeps the bits
+  // it has in a pass of <= 16 rows)
+  int mlp_rows = 0;
+  FfnRoute ffn_full = FFN_GEMMS, ffn_tail = FFN_GEMMS;   // a chunk of mlp_rows rows; the shorter last one
+};
+static LmPlan lm_plan(vv_ctx* c, int ntok, int keys) {
   const vv_config& k = c->cfg;
-  if (c->mlp_form == vv_ctx::MLP_MIXED) return false;
-  const bool w8 = c->mlp_form == vv_ctx::MLP_W8, small = P.ntok <= 2;
-  if (w8 && !(g_lm_ffn_w8 & (small ? 1 : 2))) return false;
-  const bool shape = small ? lm_ffn_fits(w8, k.hidden, k.intermediate, P.ntok)
-                           : (g_lm_ffn & 2) == 0 && c->lf_slab.p && lm_ffn16_fits(w8, k.hidden, k.intermediate, P.ntok);
-  return g_lm_ffn && c->lf_sync.p && !P.prefill && c->tp_size == 1 && !c->comm && !P.hm.idx && P.hm.sT == k.hidden &&
-         P.hm.T >= P.ntok && shape && persist_on(c);
+  const int sw_attn = g_lm_attn, sw_ffn = g_lm_ffn, sw_ffn_w8 = g_lm_ffn_w8;
+  LmPlan p;
+  // (keys < 1 -- vv_lm_mlp_replay, vv_lm_ffn_active: no attention half, no prefill; lm_attn_fits refuses it)
+  if (keys > 0) p.attn = attn_pass_plan(ntok, c->lm_slots, k.head_dim, k.n_kv_heads, keys);
+  // what every grid-waiting LM kernel asks of the pass and the context
+  const bool grid = !p.attn.prefill && c->tp_size == 1 && !c->comm && persist_on(c);
+  p.la = lm_attn_route(lm_attn_opts(c), ntok, keys);
+  p.la.one = sw_attn && grid && c->la_part.p && lm_attn_route_fits(c, p.la, ntok, keys) &&
+             lm_attn_part_floats(ntok, keys) * sizeof(float) <= c->la_part.bytes;
+  p.la_variant = 7 ^ (sw_attn >> 1);
+  p.stage_kv = c->kv_dtype && !p.la.one;
+  p.mlp_rows = ntok > LA_ROWS && p.la.one ? LA_ROWS : ntok;
+  const auto ffn = [&](int rows) {
+    const bool w8 = c->mlp_form == vv_ctx::MLP_W8, small = rows <= 2;
+    if (!sw_ffn || !grid || c->mlp_form == vv_ctx::MLP_MIXED || (w8 && !(sw_ffn_w8 & (small ? 1 : 2)))) return FFN_GEMMS;
+    if (small) return lm_ffn_fits(w8, k.hidden, k.intermediate, rows) ? FFN_ONE : FFN_GEMMS;
+    return !(sw_ffn & 2) && c->lf_slab.p && lm_ffn16_fits(w8, k.hidden, k.intermediate, rows) ? FFN_ONE16 : FFN_GEMMS;
+  };
+  p.ffn_full = ffn(p.mlp_rows);
+  p.ffn_tail = ffn(ntok % std::max(1, p.mlp_rows));
+  return p;
+}
+extern "C" int vv_lm_attn_active(vv_ctx* c, int ntok, int max_pos_p1) {
+  return c && c->finalized && lm_plan(c, ntok, max_pos_p1).la.one ? 1 : 0;
 }
 extern "C" int vv_lm_ffn_active(vv_ctx* c, int ntok) {
-  LmPass P;
-  P.ntok = ntok;
-  P.hm = rowmap(nullptr, c->cfg.hidden);
-  return c && c->finalized && lm_ffn_on(c, P) ? 1 : 0;
+  return c && c->finalized && lm_plan(c, ntok, 0).ffn_full != FFN_GEMMS ? 1 : 0;
 }
 
-// post_attention_layernorm .. down_proj (+ residual on rank 0)
+struct LmPass {
+  int ntok = 0;
+  int maxp = 0;   // keys of the longest row (max position + 1)
+  LmPlan plan;
+  bf16 *h = nullptr, *q = nullptr, *att = nullptr, *act = nullptr;
+  RowMap in_m, hm;
+  const int *slot = nullptr, *pos = nullptr;
+};
+
+static int lm_begin(vv_ctx* c, LmPass& P, int ntok, const void* embeds, int embed_rows, const int* slot,
+                    const int* pos, int max_pos_p1) {
+  if (!c->finalized) FAIL("vv_lm_forward before vv_finalize");
+  if (max_pos_p1 > c->cfg.max_ctx) FAIL("position beyond max_ctx");
+  const vv_config& k = c->cfg;
+  const int H = k.hidden, d = k.head_dim, I = k.intermediate, nhd = k.n_heads * d;
+  const size_t per = (size_t)H * 3 + c->qkv_n + nhd * 2 + I;
+  if (c->kv_dtype) CHK(kv_stage_ensure(c, (size_t)ntok));
+  if ((size_t)ntok > c->lm_ws_tokens) {
+    // + 16 act rows: a packed act block (vv_norm_pack) rounds the rows up to 16
+    CHK(c->lm_ws.ensure((per * ntok + (size_t)16 * I) * sizeof(bf16) + 256));
+    c->lm_ws_tokens = ntok;
+  }
+  P.ntok = ntok;
+  P.maxp = max_pos_p1;
+  P.h = (bf16*)c->lm_ws.p;
+  bf16* a = P.h + (size_t)ntok * H;
+  bf16* qkv = a + (size_t)ntok * H;
+  P.q = qkv + (size_t)ntok * c->qkv_n;
+  P.att = P.q + (size_t)ntok * nhd;
+  P.act = P.att + (size_t)ntok * nhd;
+  P.plan = lm_plan(c, ntok, max_pos_p1);
+  const AttnPassPlan& ap = P.plan.attn;
+  if (ap.nsplit > 1) {
+    if ((size_t)ntok * k.n_kv_heads * std::max(1, ap.ngroups) > 65536) FAIL("attention split tickets exhausted");
+    CHK(c->attn_part.ensure(attn_part_bytes(ntok, k.n_heads, ap.nsplit, ap.ngroups)));
+  }
+  // token row m reads embeds row m % embed_rows (the negative CFG rows consume the
+  // positive rows' embeddings, :594-596); layer 0's attention residual writes h
+  if (embed_rows <= 0 || embed_rows > ntok) embed_rows = ntok;
+  P.in_m = rowmap(embeds, H, embed_rows, 0);
+  P.hm = rowmap(P.h, H);   // (the one-launch kernels rely on it: dense rows of stride H, no index, every row of the pass)
+  P.slot = slot;
+  P.pos = pos;
+  return 0;
+}
+
+// input_layernorm .. o_proj (+ residual on rank 0)
+static int lm_attn_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
+  const vv_config& k = c->cfg;
+  const int H = k.hidden, d = k.head_dim, nhd = k.n_heads * d;
+  const LmLayerW& w = c->lmw[l];
+  const LmPlan& plan = P.plan;
+  {
+    // input_layernorm -> q|k|v projection (+bias) -> RoPE -> q / KV cache, one launch
+    GemmArgs g = gemm_args(c, P.ntok, c->qkv_n, H, l == 0 ? P.in_m : P.hm, w.qkv, EPI_ROPE, RowMap{},
+                           w.qkv_b);
+    g.xf = xf_norm(w.in_norm, k.rms_eps);
+    g.rope.nh = k.n_heads;
+    g.rope.nkv = k.n_kv_heads;
+    g.rope.layer = l;
+    g.rope.q_out = P.q;
+    g.rope.slots = P.slot;
+    g.rope.pos = P.pos;
+    g.rope.inv_freq = c->lm.inv_freq;
+    g.rope.cs_tab = g_rope_tab ? (const bf16*)c->rope_tab.p : nullptr;
+    g.rope.kv = c->kv;
+    // (k_lm_attn's KVQ forms stage and quantise inside the launch: the real tables, no prep, no k_kv_quant)
+    if (plan.stage_kv) {
+      // FP8 KV: the epilogue appends to the staging cache (token m at slot 0, position m; cos / sin
+      // from the pass's rows of the real positions), k_kv_quant below moves the rows to the cache
+      if (l == 0)
+        KCHK(launch_kv_stage_prep(P.ntok, (int)c->kv_stage_tokens, P.pos, c->kv.max_ctx, (const bf16*)c->rope_tab.p, c->stg_cs, c->stg_slot,
+                                  c->stg_pos, st));
+      g.rope.slots = c->stg_slot;
+      g.rope.pos = c->stg_pos;
+      g.rope.cs_tab = c->stg_cs;
+      g.rope.kv = c->stg;
+    }
+    if (plan.la.one) {
+      LmAttnArgs a;
+      memset(&a, 0, sizeof(a));
+      a.qkv = g;
+      a.kvq = plan.la.kvq;
+      a.stg = c->stg;
+      a.kv8 = c->kv8;
+      a.nw = w.in_norm;
+      a.eps = k.rms_eps;
+      a.scale = 1.0f / sqrtf((float)d);
+      a.R = P.ntok;
+      a.ow = w.o.w;
+      a.ow8 = w.o.w8;     // codes throughout: the launcher picks the W8 form (a.qkv carries q|k|v's)
+      a.owe = w.o.w8e;
+      a.res =l == 0 ? P.in_m : P.hm;
+      a.out = P.hm;
+      a.att = P.att;
+      a.part = (float*)c->la_part.p;
+      a.sync = (unsigned*)c->lf_sync.p;
+      a.err = err_word(c);
+      a.stamps = g_lm_attn_stamps.load();
+      a.variant = plan.la_variant;
+      KCHK(launch_lm_attn(a, P.maxp, st));
+      return 0;
+    }
+    CHK(gemm(c, g, st));
+    if (plan.stage_kv)
+      KCHK(launch_kv_quant(c->stg, c->kv, c->kv8, l, k.n_kv_heads, c->lm_slots, P.ntok, P.slot, P.pos, st));
+  }
+  AttnArgs at;
+  memset(&at, 0, sizeof(at));
+  at.kv8 = c->kv8;
+  at.stamps = g_attn_stamps;
+  at.nq = P.ntok;
+  at.nh = k.n_heads;
+  at.nkv = k.n_kv_heads;
+  at.layer = l;
+  at.nsplit = plan.attn.nsplit;
+  at.chunk = plan.attn.chunk;
+  at.prefill = plan.attn.prefill;
+  at.defer = plan.attn.defer;
+  at.counters = (unsigned*)c->attn_cnt.p;
+  at.scale = 1.0f / sqrtf((float)d);
+  at.q = P.q;
+  at.out = P.att;
+  at.slots = P.slot;
+  at.pos = P.pos;
+  at.kv = c->kv;
+  at.group = plan.attn.group;
+  at.ngroups = plan.attn.ngroups;
+  attn_part_carve(at, c->attn_part.p);
+  KCHK(launch_attn(at, st));
+  GemmArgs g = gemm_args(c, P.ntok, H, nhd, rowmap(P.att, nhd), w.o, EPI_RES, P.hm);
+  if (at.defer || at.group) attn_merge_xf(g, at);
+  tp_residual(c, g, l == 0 ? P.in_m : P.hm);
+  CHK(gemm(c, g, st));
+  return 0;
+}
+
+// post_attention_layernorm .. down_proj (+ residual on rank 0), chunk by chunk (LmPlan::mlp_rows)
 static int lm_mlp_half(vv_ctx* c, LmPass& P, int l, hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, I = k.intermediate;
   const LmLayerW& w = c->lmw[l];
-  if (P.ntok > LA_ROWS && lm_attn_on(c, P)) {
-    // a pass whose attention half ran k_lm_attn's second row class (lm_attn_max_rows): the MLP runs as the
-    // passes of <= LA_ROWS rows it is made of, rows [0, 16) and [16, ntok), each as such a pass runs it
-    // (k_lm_ffn16 / k_lm_ffn where they apply).  The GEMMs of 17 .. 32 rows sum K in another order, so
-    // this is what keeps every row of the pass on the bits it has in a pass of at most 16 rows.
-    for (int r0 = 0; r0 < P.ntok; r0 += LA_ROWS) {
-      LmPass S = P;
-      S.ntok = std::min(LA_ROWS, P.ntok - r0);
-      S.hm = rowmap((bf16*)P.hm.base + (size_t)r0 * H, H);
-      S.act = P.act + (size_t)r0 * I;
-      CHK(lm_mlp_half(c, S, l, st));
+  for (int r0 = 0; r0 < P.ntok; r0 += P.plan.mlp_rows) {
+    const int n = std::min(P.plan.mlp_rows, P.ntok - r0);
+    const FfnRoute route = n == P.plan.mlp_rows ? P.plan.ffn_full : P.plan.ffn_tail;
+    bf16* const h = (bf16*)P.hm.base + (size_t)r0 * H;
+    bf16* const act = P.act + (size_t)r0 * I;
+    if (route != FFN_GEMMS) {
+      LmFfnArgs a;
+      memset(&a, 0, sizeof(a));
+      a.x = h;
+      a.out = h;
+      a.ldx = H;
+      a.R = n;
+      a.eps = k.rms_eps;
+      a.nw = w.post_norm;
+      a.gu = w.gu.w;
+      a.dn = w.down.w;
+      a.gu8 = w.gu.w8;     // MLP_W8: the code forms (the launchers pick the W8 kernels)
+      a.gue = w.gu.w8e;
+      a.dn8 = w.down.w8;
+      a.dne = w.down.w8e;
+      a.act = act;
+      a.sync = (unsigned*)c->lf_sync.p;
+      a.err = err_word(c);
+      a.slab = (float*)c->lf_slab.p;
+      a.stamps = g_lm_ffn_stamps.load();
+      if (route == FFN_ONE) KCHK(launch_lm_ffn(a, st));
+      else KCHK(launch_lm_ffn16(a, st));
+      continue;
     }
-    return 0;
+    // post_attention_layernorm fused into gate|up's A load
+    const RowMap hm = rowmap(h, H);
+    GemmArgs g = gemm_args(c, n, 2 * I, H, hm, w.gu, EPI_SILU_MUL, rowmap(act, I));
+    g.xf = xf_norm(w.post_norm, k.rms_eps);
+    GemmArgs d = gemm_args(c, n, H, I, rowmap(act, I), w.down, EPI_RES, hm);
+    tp_residual(c, d, hm);
+    // prefill: SiLU*up written MFMA-fragment-packed for the down projection when
+    // both take the 256 x 256 tile (16K rows: down 449 -> 388 us)
+    GemmArgs gp = g;
+    gp.xf.kind = XF_NONE;
+    if (g_norm_pack && I % 32 == 0 && gemm_uses_xl(gp) && gemm_uses_xl(d)) {
+      g.epi.pack = 1;
+      d.apack = 1;
+    }
+    CHK(gemm(c, g, st));
+    CHK(gemm(c, d, st));
   }
-  if (lm_ffn_on(c, P)) {
-    LmFfnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const bf16*)P.hm.base;
-    a.out = (bf16*)P.hm.base;
-    a.ldx = H;
-    a.R = P.ntok;
-    a.eps = k.rms_eps;
-    a.nw = w.post_norm;
-    a.gu = w.gu.w;
-    a.dn = w.down.w;
-    a.gu8 = w.gu.w8;     // MLP_W8: the code forms (the launchers pick the W8 kernels)
-    a.gue = w.gu.w8e;
-    a.dn8 = w.down.w8;
-    a.dne = w.down.w8e;
-    a.act = P.act;
-    a.sync = (unsigned*)c->lf_sync.p;
-    a.err = err_word(c);
-    a.slab = (float*)c->lf_slab.p;
-    a.stamps = g_lm_ffn_stamps.load();
-    if (P.ntok <= 2) KCHK(launch_lm_ffn(a, st));
-    else KCHK(launch_lm_ffn16(a, st));
-    return 0;
-  }
-  // post_attention_layernorm fused into gate|up's A load
-  GemmArgs g = gemm_args(c, P.ntok, 2 * I, H, P.hm, w.gu, EPI_SILU_MUL, rowmap(P.act, I));
-  g.xf = xf_norm(w.post_norm, k.rms_eps);
-  GemmArgs d = gemm_args(c, P.ntok, H, I, rowmap(P.act, I), w.down, EPI_RES, P.hm);
-  tp_residual(c, d, P.hm);
-  // prefill: SiLU*up written MFMA-fragment-packed for the down projection when
-  // both take the 256 x 256 tile (16K rows: down 449 -> 388 us)
-  GemmArgs gp = g;
-  gp.xf.kind = XF_NONE;
-  if (g_norm_pack && I % 32 == 0 && gemm_uses_xl(gp) && gemm_uses_xl(d)) {
-    g.epi.pack = 1;
-    d.apack = 1;
-  }
-  CHK(gemm(c, g, st));
-  CHK(gemm(c, d, st));
   return 0;
 }
 
 // Diagnostic (bench.py's roofline of the LM MLP block): `reps` passes over the
 // LM layers' MLP blocks alone on `ntok` decode rows (hidden [ntok][H], act
 // [ntok][I] scratch), as lm_mlp_half runs them (k_lm_ffn or the GEMV pair).
+// The call has no key count, so its plan has no attention half: a pass of 17 .. 32
+// rows runs whole, never as the 16-row chunks of k_lm_attn's second row class.
 extern "C" int vv_lm_mlp_replay(vv_ctx* c, int ntok, void* hidden, void* act, int reps, vv_stream vst) {
   if (!c || !c->finalized || ntok < 1 || ntok > 2 * c->cfg.max_batch || !hidden || !act)
     FAIL("vv_lm_mlp_replay: bad arguments");
   LmPass P;
   P.ntok = ntok;
+  P.plan = lm_plan(c, ntok, 0);
   P.h = (bf16*)hidden;
   P.hm = rowmap(hidden, c->cfg.hidden);
   P.act = (bf16*)act;

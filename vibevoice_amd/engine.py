@@ -10,8 +10,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .schedule import Schedule
-from .weights import (W8_CODES, check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_max_rows, check_lm_attn_w8, check_weight_dtype, codec_channels, head_tp_check,
-                      pack)
+from .weights import check_lm_options, codec_channels, head_tp_check, pack
 
 _VALID_IDS_DEFAULT = None
 
@@ -116,16 +115,10 @@ class Engine:
         the bits it computes in a pass of at most 16 rows; bf16 KV -- an FP8-KV engine keeps
         its launches above 16 rows).  tp_size 1 only.  Combines with lm_attn_max_keys and
         lm_attn_w8."""
-        self.lm_attn_max_keys = check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
-        self.lm_attn_max_rows = check_lm_attn_max_rows(lm_attn_max_rows, tp_size)
+        opts = check_lm_options(weight_dtype, kv_dtype, lm_attn_w8, lm_attn_kv8, lm_attn_max_keys, lm_attn_max_rows,
+                                max_ctx=max_ctx, tp_size=tp_size, packed=packed)
         persistent = normalize_persistent(persistent)
-        check_weight_dtype(weight_dtype, tp_size)
-        check_kv_dtype(kv_dtype, tp_size)
-        self.lm_attn_kv8 = check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
-        packed_fp8 = packed is not None and any(k.endswith("_w" + W8_CODES) for k in packed)
-        self.lm_attn_w8 = check_lm_attn_w8(lm_attn_w8, weight_dtype if packed is None else "fp8_e4m3" if packed_fp8 else None,
-                                           kv_dtype, tp_size, lm_attn_kv8=self.lm_attn_kv8)
-        self.kv_dtype = kv_dtype
+        self.__dict__.update(opts)   # .weight_dtype (with `packed`: theirs), .kv_dtype, .lm_attn_w8 / _kv8 / _max_keys / _max_rows
         L = _lib.lib()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -144,9 +137,6 @@ class Engine:
             self.w = packed if packed is not None else pack(state_dict, cfg, self.device, tp_rank=tp_rank,
                                                             tp_size=tp_size, tp_head=self.tp_head,
                                                             weight_dtype=weight_dtype)
-            if packed is not None:
-                weight_dtype = "fp8_e4m3" if any(k.endswith("_w" + W8_CODES) for k in packed) else None
-            self.weight_dtype = weight_dtype
             h = ctypes.c_void_p()
             self._ecfg = engine_config(cfg, max_batch, max_ctx, tp_size, self.tp_head)
             _lib.check(L.vv_create(ctypes.byref(self._ecfg), self.device.index or 0, ctypes.byref(h)), "create")
@@ -159,16 +149,13 @@ class Engine:
                     _lib.check(L.vv_tp_shard_head(h, 1), "tp_shard_head")
             if persistent is not True:
                 _lib.check(L.vv_set_persistent(h, 2 if persistent == "follow" else 0), "set_persistent")
-            if kv_dtype is not None:
-                _lib.check(L.vv_set_kv_dtype(h, 1), "set_kv_dtype")
-            if self.lm_attn_w8:
-                _lib.check(L.vv_set_lm_attn_w8(h, 1), "set_lm_attn_w8")
-            if self.lm_attn_kv8:
-                _lib.check(L.vv_set_lm_attn_kv8(h, 1), "set_lm_attn_kv8")
-            if self.lm_attn_max_keys is not None:
-                _lib.check(L.vv_set_lm_attn_max_keys(h, self.lm_attn_max_keys), "set_lm_attn_max_keys")
-            if self.lm_attn_max_rows is not None:
-                _lib.check(L.vv_set_lm_attn_max_rows(h, self.lm_attn_max_rows), "set_lm_attn_max_rows")
+            # (setter, value, is the default: the setter is not called)
+            for name, value, default in (("kv_dtype", 1, kv_dtype is None), ("lm_attn_w8", 1, not self.lm_attn_w8),
+                                         ("lm_attn_kv8", 1, not self.lm_attn_kv8),
+                                         ("lm_attn_max_keys", self.lm_attn_max_keys, self.lm_attn_max_keys is None),
+                                         ("lm_attn_max_rows", self.lm_attn_max_rows, self.lm_attn_max_rows is None)):
+                if not default:
+                    _lib.check(getattr(L, "vv_set_" + name)(h, value), "set_" + name)
             for name, t in self.w.items():
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
                 _lib.check(L.vv_bind_weight(h, name.encode(), _ptr(t), shape, t.dim()), f"bind {name}")

@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .config import VibeVoiceConfig
 from .engine import Engine
-from .weights import check_kv_dtype, check_lm_attn_kv8, check_lm_attn_max_keys, check_lm_attn_max_rows, check_lm_attn_w8, check_weight_dtype, head_tp_default, synthetic_state_dict
+from .weights import check_kv_dtype, check_lm_options, head_tp_default, synthetic_state_dict
 
 
 @dataclass
@@ -214,48 +214,28 @@ class VibeVoiceForConditionalGenerationInference:
         else ValueError; bf16 KV -- with kv_dtype="fp8_e4m3" passes above 16 rows keep their
         launches).  Measured: DESIGN.md §3 "k_lm_attn at 17 to 32 rows"."""
         max_ctx = min(max_ctx, config.decoder_config.max_position_embeddings)
-        check_lm_attn_max_keys(lm_attn_max_keys, max_ctx)
-        self.lm_attn_max_keys = lm_attn_max_keys
-        check_lm_attn_max_rows(lm_attn_max_rows)
-        self.lm_attn_max_rows = lm_attn_max_rows
-        check_weight_dtype(weight_dtype)
-        check_kv_dtype(kv_dtype)
-        check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
-        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
-        self.weight_dtype = weight_dtype
-        self.kv_dtype = kv_dtype
-        self.lm_attn_w8 = bool(lm_attn_w8)
-        self.lm_attn_kv8 = lm_attn_kv8
+        tp_rank, tp_size, uid = 0, 1, None
+        if tp_group is not None:
+            import torch.distributed as dist
+            tp_rank, tp_size = dist.get_rank(tp_group), dist.get_world_size(tp_group)
+        opts = check_lm_options(weight_dtype, kv_dtype, lm_attn_w8, lm_attn_kv8, lm_attn_max_keys, lm_attn_max_rows,
+                                max_ctx=max_ctx, tp_size=tp_size)
+        self.__dict__.update(opts)   # .weight_dtype, .kv_dtype, .lm_attn_w8, .lm_attn_kv8, .lm_attn_max_keys, .lm_attn_max_rows
         self.config = config
         self.attn_implementation = attn_implementation
         self.device = torch.device(device)
         self.dtype = torch.bfloat16
         self._sd = state_dict
-        tp_rank, tp_size, uid = 0, 1, None
-        if tp_group is not None:
-            import torch.distributed as dist
-            tp_rank, tp_size = dist.get_rank(tp_group), dist.get_world_size(tp_group)
-            check_weight_dtype(weight_dtype, tp_size)
-            check_kv_dtype(kv_dtype, tp_size)
-            check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
-            check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size, lm_attn_kv8=lm_attn_kv8)
-            check_lm_attn_max_keys(lm_attn_max_keys, max_ctx, tp_size)
-            check_lm_attn_max_rows(lm_attn_max_rows, tp_size)
-            if tp_size > 1:
-                box = [Engine.tp_unique_id() if tp_rank == 0 else None]
-                dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
-                uid = box[0]
+        if tp_size > 1:
+            box = [Engine.tp_unique_id() if tp_rank == 0 else None]
+            dist.broadcast_object_list(box, src=dist.get_global_rank(tp_group, 0), group=tp_group)
+            uid = box[0]
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.tp_head = head_tp_default(config, tp_size) if tp_head is None else bool(tp_head and tp_size > 1)
         self.engine = Engine(config, state_dict, self.device, max_batch=max_batch, tp_head=self.tp_head,
                              max_ctx=max_ctx,
                              tp_rank=tp_rank, tp_size=tp_size, tp_unique_id=uid, persistent=persistent,
-                             **({} if weight_dtype is None else {"weight_dtype": weight_dtype}),
-                             **({} if kv_dtype is None else {"kv_dtype": kv_dtype}),
-                             **({"lm_attn_w8": True} if lm_attn_w8 else {}),
-                             **({"lm_attn_kv8": True} if lm_attn_kv8 else {}),
-                             **({} if lm_attn_max_keys is None else {"lm_attn_max_keys": lm_attn_max_keys}),
-                             **({} if lm_attn_max_rows is None else {"lm_attn_max_rows": lm_attn_max_rows}))
+                             **{k: v for k, v in opts.items() if v not in (None, False)})   # (the defaults stay Engine's)
         self.ddpm_inference_steps = config.diffusion_head_config.ddpm_num_inference_steps
         self.model = _ModelView(self)
         self.use_graphs = True          # capture the steady-state loop body into hipGraphs
@@ -323,12 +303,8 @@ class VibeVoiceForConditionalGenerationInference:
         that many keys run the one-launch LM attention kernel (its long form past 4,096).
         `lm_attn_max_rows`: None, or an int in [16, 32]: decode passes of up to that many rows
         (B up to half of it) run the one-launch LM attention kernel."""
-        check_weight_dtype(weight_dtype)
-        check_kv_dtype(kv_dtype)
-        check_lm_attn_kv8(lm_attn_kv8, kv_dtype)
-        check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, lm_attn_kv8=lm_attn_kv8)
-        check_lm_attn_max_keys(lm_attn_max_keys, 1 << 30)   # (the type; the constructor checks the range against its max_ctx)
-        check_lm_attn_max_rows(lm_attn_max_rows)
+        check_lm_options(weight_dtype, kv_dtype, lm_attn_w8, lm_attn_kv8, lm_attn_max_keys, lm_attn_max_rows,
+                         max_ctx=None)   # (the constructor checks lm_attn_max_keys' range against its max_ctx)
         resolve_dtype(torch_dtype)
         dev = resolve_device(device_map)
         if str(path).startswith("synthetic:"):

@@ -305,6 +305,25 @@ def check_lm_attn_w8(lm_attn_w8, weight_dtype=None, kv_dtype=None, tp_size=1, *,
     return bool(lm_attn_w8)
 
 
+def check_lm_options(weight_dtype, kv_dtype, lm_attn_w8, lm_attn_kv8, lm_attn_max_keys, lm_attn_max_rows, *,
+                     max_ctx, tp_size=1, packed=None):
+    """Every check of the LM's format and kernel options, in one order (the first invalid
+    one raises); returns them normalised, by keyword.  max_ctx=None checks
+    lm_attn_max_keys' type only (a caller that does not know its engine's max_ctx yet).
+    packed: another engine's packed weights -- the weight format is then theirs,
+    whatever `weight_dtype` says."""
+    keys = check_lm_attn_max_keys(lm_attn_max_keys, float("inf") if max_ctx is None else max_ctx, tp_size)
+    rows = check_lm_attn_max_rows(lm_attn_max_rows, tp_size)
+    check_weight_dtype(weight_dtype, tp_size)
+    check_kv_dtype(kv_dtype, tp_size)
+    kv8 = check_lm_attn_kv8(lm_attn_kv8, kv_dtype, tp_size)
+    if packed is not None:
+        weight_dtype = "fp8_e4m3" if any(k.endswith("_w" + W8_CODES) for k in packed) else None
+    w8 = check_lm_attn_w8(lm_attn_w8, weight_dtype, kv_dtype, tp_size, lm_attn_kv8=kv8)
+    return dict(weight_dtype=weight_dtype, kv_dtype=kv_dtype, lm_attn_w8=w8, lm_attn_kv8=kv8,
+                lm_attn_max_keys=keys, lm_attn_max_rows=rows)
+
+
 def _pow2(k):
     """2.0 ** k (int tensor, -126 <= k <= 127) as float32, built from the exponent
     bits: exact on every device.  (torch.ldexp multiplies by pow(2.0, k), which a
