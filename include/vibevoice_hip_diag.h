@@ -193,7 +193,8 @@ int vv_gemm_tune_apack(int on);
  * GEMV pair, not bitwise) while ctx is the device's only registered context;
  * 0 = gate|up + down GEMV launches. */
 int vv_head_m16(int on);
-/* Test query: 1 when a head layer of n samples on ctx would run head_m16 now. */
+/* Test query: the m16 word of vv_diag_head_plan: 1 when a head layer of n
+ * samples on ctx would run head_m16 now. */
 int vv_head_m16_active(vv_ctx* ctx, int n);
 /* Diagnostic: per-workgroup s_memrealtime stamps of every head_m16 launch into
  * buf ([256][16] u64, overwritten per launch; NULL = off). */
@@ -217,9 +218,9 @@ int vv_lm_ffn_w8(int bits);
  * u64, overwritten per launch; NULL = off). */
 int vv_lm_ffn_stamps(void* buf);
 /* Diagnostic switch: the diffusion head's step boundary (final layer + DPM of
- * step s, noisy projection of step s + 1) as one launch at 2n <= 4 rows
- * (head_fin.hip; 1, default) or the two GEMV launches (0); and whether it
- * applies to this context at n samples. */
+ * step s, noisy projection of step s + 1) as one launch at 2n <= 16 rows
+ * (head_fin.hip; 1, default) or the two GEMV launches (0); and the fin word of
+ * vv_diag_head_plan: whether it applies to this context at n samples now. */
 int vv_head_fin(int on);
 int vv_head_fin_active(vv_ctx* ctx, int n);
 /* Diagnostic switch: the LM attention half at decode (input_layernorm .. o_proj
@@ -290,6 +291,24 @@ int vv_head_m16_pre(int on);
  * n samples, then `reps` passes over its FFN layers alone (the kernels the loop
  * runs for them at this n), asynchronously on st. */
 int vv_head_layers_replay(vv_ctx* ctx, int n, const void* pos_h, const void* neg_h, int reps, vv_stream st);
+/* Diagnostic: how a diffusion sample of R = 2n rows picks its kernels,
+ * as a function of plain values -- vv_tp_shard_head, whether the head is bound in
+ * the GEMV layout, the TP size and whether a communicator exists; the values
+ * given to vv_head_m16 / vv_head_m16_pre / vv_head_fin; whether the grid-waiting
+ * kernels run on the context now (vv_persistent_active); the schedule's steps;
+ * the bytes of the head layers' weights; what head_m16.hip and head_fin.hip
+ * answer for the shape at R rows.  out[0..10] = (R, keep, sharded, m16, pre,
+ * a_first, late_down, fin, nfused, s0, epi_dpm): keep = the weights stay cache
+ * resident; m16 = a layer is one k_head_m16 launch, with pre (the distributed A
+ * side: the noisy projection is then k_head_noisy16), a_first and late_down as
+ * its arguments; fin = the steps [s0, s0 + nfused) end in k_head_fin; epi_dpm =
+ * CFG + DPM is the final GEMM's epilogue, not k_cfg_dpm.  The function every
+ * sample, vv_head_layers_replay and the two _active queries evaluate.
+ * vv_diag_head_plan: the same words for n samples on a finalized ctx now (cap:
+ * the caller's capacity in words, >= 11). */
+int vv_diag_head_route(int head_tp, int head_gemv, int tp_size, int comm, int m16, int m16_pre, int fin, int persist,
+                       int steps, int R, long long wbytes, int fit_m16, int fit_fin, int* out);
+int vv_diag_head_plan(vv_ctx* ctx, int n, int* out, int cap);
 /* Test hook: raise the engine's grid-wait error word as a wait that gave up
  * would, and leave its wait counters part-advanced as such a launch does
  * (synchronises the device first): in each of the three counter buffers shard 0,
@@ -322,9 +341,11 @@ int vv_codec_tile(int on);
 int vv_codec_tile_stamps(void* buf);
 /* A/B / test switch: 1 (default) = each wide codec stage (C = 256 / 512) as ONE
  * launch of workgroup clusters (codec_wide.hip) where the grid-waiting kernels
- * run; 0 = k_mix + fc1 / fc2 GEMMs per Block1D.  _active: whether a codec step
- * of n samples on ctx runs them now.  _stamps: per-workgroup phase stamps
- * ([n][tiles x S][16] u64 at buf + 8192 x (2 x net + (C == 512))); NULL = off. */
+ * run; 0 = k_mix + fc1 / fc2 GEMMs per Block1D.  _active: whether some
+ * acoustic-decoder stage of a codec step of n samples on ctx runs as such a
+ * launch now (the wide route of vv_diag_codec_plan, below).  _stamps:
+ * per-workgroup phase stamps ([n][tiles x S][16] u64 at buf + 8192 x (2 x net +
+ * (C == 512))); NULL = off. */
 int vv_codec_wide(int on);
 /* Diagnostic: wide-stage grids past one resident wave (1: clusters complete in
  * dispatch order; slower at B = 8 than the GEMM path) or only grids resident at
@@ -379,8 +400,32 @@ int vv_codec_mix_fusion(int mask);
  * context registered for persistent kernels; 0 = one launch per GEMV. */
 int vv_codec_stage(int on);
 /* Test query: 1 when a one-sample codec step on ctx would run the acoustic
- * decoder's first stage as the persistent launch now. */
+ * decoder's first stage as the persistent launch now (stage 0 of
+ * vv_diag_codec_plan(ctx, 0, 1), below, takes the persistent route). */
 int vv_codec_stage_active(vv_ctx* ctx);
+/* Diagnostic: how one codec stage picks its kernels, as a function of
+ * plain values -- the values given to vv_codec_stage / _wide / _tile /
+ * _mix_fusion; whether the grid-waiting kernels run on the context now (the
+ * two kernels' sync buffers exist in every finalized context); the stage (net,
+ * index i of nst, channels C, rows T, blocks, mixer history ctx, ratio rat and
+ * channels Cn of the transition before it, the stem's in_ch); and what
+ * codec_tile_fits, codec_wide_fits (with the one sync line per cluster),
+ * codec_stage_fits, block_lds and gemv_mix_lds answer for it (vv_codec_wide_over
+ * acts through the second).  out[0..5] = (route, pre, post, own_pre, xf_mix, R):
+ * route 0 one tile launch, 1 one launch of clusters, 2 one persistent launch, 3
+ * one k_block per Block1D, 4 fc1 / fc2 GEMMs per Block1D; pre / post = the
+ * CT_PRE_* transition and CT_POST_* head conv inside a tile launch; own_pre = the
+ * transition before the stage (stage 0: the stem) is a launch of its own; xf_mix
+ * (route 4) = the mixer runs in fc1's prologue, not as k_mix; R (routes 3, 4) =
+ * rows per mixer workgroup.  The function every codec run and vv_finalize evaluate.
+ * vv_diag_codec_plan: a step of n samples on a finalized ctx now, net 0 = the
+ * acoustic decoder, 1 = the semantic encoder: out = (stages, own_head, then the
+ * six words per stage); own_head = the head conv is a launch of its own; cap:
+ * the caller's capacity in words (fails, writing nothing, when short). */
+int vv_diag_codec_route(int stage, int wide, int tile, int fusion, int persist, int decoder, int i, int nst, int C,
+                        int T, int depth, int ctx, int rat, int Cn, int in_ch, int fit_tile, int fit_wide,
+                        int fit_stage, int fit_block, int fit_mix, int* out);
+int vv_diag_codec_plan(vv_ctx* ctx, int net, int n, int* out, int cap);
 /* Diagnostic: the acoustic decoder's persistent launch of stage `stage`
  * records per-workgroup s_memrealtime stamps into buf ([256][64] u64;
  * nullptr: off). */

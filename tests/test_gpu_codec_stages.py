@@ -263,6 +263,49 @@ def stream(G, eng, lay, sched, tag, seed, full_frame=1, before_frame=None):
     return seen
 
 
+TILE, WIDE, STAGE, BLOCKS, GEMMS = range(5)     # vv_diag_codec_plan's routes
+CHANS = ([2048, 1024, 512, 256, 128, 64, 32], [32, 64, 128, 256, 512, 1024, 2048])   # decoder, encoder
+# the stages the mixer fits fc1's prologue at (<= 16 rows of <= 4 samples within 96 KB of LDS): (C, T) -> the n
+XF_MIX = {(2048, 1): (1, 2), (1024, 8): (1,)}
+
+
+def check_plan(eng, n, forms, fusion):
+    """vv_diag_codec_plan of both nets at n samples against the routes the case's docstring names: forms = the
+    one-launch stages (persistent, clusters, tiles) are on; fusion = vv_codec_mix_fusion's mask."""
+    L = _lib.lib()
+    wide_dec = 0
+    for net in (0, 1):
+        w = (ctypes.c_int * 64)()
+        assert L.vv_diag_codec_plan(eng.h, net, n, w, 43) != 0                   # capacity short: fails
+        _lib.check(L.vv_diag_codec_plan(eng.h, net, n, w, 64), "diag_codec_plan")
+        assert w[0] == 7
+        st = [tuple(w[2 + 6 * i: 8 + 6 * i]) for i in range(7)]
+        print(f"codec plan net {net} n={n} forms={forms} fusion={fusion}: own_head {w[1]} {st}")
+        for i, (route, pre, post, own_pre, xf_mix, R) in enumerate(st):
+            C = CHANS[net][i]
+            T = 3200 * 32 // C if C <= 128 else {256: 200, 512: 40, 1024: 8, 2048: 1}[C]
+            if C <= 128:                         # tiles; k_block per Block1D with bit 1 of the mask, else GEMMs
+                want = (TILE,) if forms else (BLOCKS,) if fusion & 2 else (GEMMS,)
+            elif C <= 512:
+                # clusters: 3 x 16 x n workgroups at C = 512, 13 x 8 x n at C = 256; the MI355X holds one 512-thread
+                # cluster workgroup on each of its 256 CUs, so C = 256 at n = 3 (312 workgroups) is not resident
+                # and keeps its GEMMs
+                want = (WIDE,) if forms and (C == 512 or n <= 2) else (GEMMS,)
+            else:                                # the persistent stage takes one sample
+                want = (STAGE,) if forms and n == 1 else (GEMMS,)
+            assert route in want, (net, i, n, st[i], want)
+            assert xf_mix == int(route == GEMMS and bool(fusion & 1) and n in XF_MIX.get((C, T), ())), (net, i, n, st[i])
+            assert R == (0 if route < BLOCKS else max(1, min(T, 2048 // C))), (net, i, n, st[i])
+            # the decoder's 2x transposed convs / head conv, the encoder's stem / 2x strided convs ride in the tiles
+            fused = route == TILE and C <= (64 if net == 0 else 128)
+            assert own_pre == int(not fused) and (pre != 0) == fused and post == int(route == TILE and net == 0 and i == 6)
+        assert w[1] == int(not (net == 0 and st[6][0] == TILE))
+        if net == 0:
+            if n == 1:
+                assert L.vv_codec_stage_active(eng.h) == int(st[0][0] == STAGE)
+            assert L.vv_codec_wide_active(eng.h, n) == int(any(s[0] == WIDE for s in st))
+
+
 SCHED = [[0, 2], [0, 1, 2], [2]]
 CASES = [("default-one", [[1]] * 3, None, (1, 1)),
          ("default-many", SCHED, None, (1, 1)),
@@ -272,7 +315,8 @@ CASES = [("default-one", [[1]] * 3, None, (1, 1)),
 
 @pytest.mark.parametrize("name,sched,fusion,active", CASES, ids=[c[0] for c in CASES])
 def test_stages_and_state(G, name, sched, fusion, active):
-    """default-one: persistent stage, wide, tile.  default-many: XF_MIX GEMVs, wide at n = 2 / 3, tile.
+    """default-one: persistent stage, wide, tile.  default-many: XF_MIX GEMVs, wide at n = 2 / 3 (C = 256: n = 2 only,
+    k_mix + GEMMs at n = 3), tile.
     per-block (stage, wide, tile off): k_block, XF_MIX, k_mix + GEMM.  gemm (+ mix fusion off): k_mix + GEMMs."""
     L = _lib.lib()
     eng, lay = make_engine(G)
@@ -285,6 +329,7 @@ def test_stages_and_state(G, name, sched, fusion, active):
         assert L.vv_codec_stage_active(eng.h) == active[0]
         for n in sorted({len(s) for s in sched}):
             assert L.vv_codec_wide_active(eng.h, n) == active[1], n
+            check_plan(eng, n, fusion is None, 3 if fusion is None else fusion)
         stream(G, eng, lay, sched, name, 51)
     finally:
         L.vv_codec_stage(1)
@@ -333,6 +378,7 @@ def test_form_hand_over(G):
             L.vv_codec_wide(on)
             L.vv_codec_tile(on)
             assert L.vv_codec_stage_active(eng.h) == on and L.vv_codec_wide_active(eng.h, 1) == on
+            check_plan(eng, 1, bool(on), 3)
         stream(G, eng, lay, [[1], [1], [1]], "hand-over", 57, before_frame=before)
     finally:
         L.vv_codec_stage(1)

@@ -327,3 +327,60 @@ def test_head_fin_one_launch_vs_oracle_and_gemv_pair(n, S, sde):
     assert torch.equal(one, outs[1][1])
     assert rel_err(one, ref) < 2e-2 and cos(one, ref) > 0.999
     assert rel_err(one, pair) < 2e-2 and cos(one, pair) > 0.999
+
+
+def test_head_plan_is_the_route_and_the_queries():
+    """vv_diag_head_plan (head_plan's words for a sample on this engine now) equals vv_diag_head_route on the same
+    plain values -- the 1.5B head shapes (both kernels take them at 2 .. 16 rows), unsharded, the GEMV layout,
+    the device's sole context -- for n in {1, 3, 8}, S in {2, 3, 10} and vv_head_m16 x vv_head_fin on / off, and
+    the two _active queries are its m16 and fin words.  One sample at n = 1, S = 3 is bitwise repeatable."""
+    import ctypes
+    from vibevoice_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(77)
+    sdh, hc, H = real_head_sd(g)
+    F = int(H * hc.head_ffn_ratio)
+    cfg = tiny_config(hidden=H, layers=1, heads=12, kv_heads=2, inter=256)
+    sd = synthetic_state_dict(cfg, seed=0, device="cpu", mode="test", with_acoustic_encoder=False)
+    for k, v in sdh.items():
+        sd["model.prediction_head." + k] = v
+    eng = Engine(cfg, sd, dev, max_batch=8, max_ctx=64)   # the GEMV layout (max_batch > 2)
+    assert eng.persistent_active()
+    wbytes = hc.head_layers * 3 * F * H * 2
+    got, want = (ctypes.c_int * 11)(), (ctypes.c_int * 11)()
+    assert L.vv_diag_head_plan(eng.h, 1, got, 10) != 0                   # capacity short: fails
+    try:
+        for S in (2, 3, 10):
+            eng.set_steps(S)
+            for n in (1, 3, 8):
+                for m16 in (0, 1):
+                    for fin in (0, 1):
+                        L.vv_head_m16(m16)
+                        L.vv_head_m16_pre(1)
+                        L.vv_head_fin(fin)
+                        _lib.check(L.vv_diag_head_plan(eng.h, n, got, 11), "diag_head_plan")
+                        assert L.vv_diag_head_route(0, 1, 1, 0, m16, 1, fin, 1, S, 2 * n, wbytes, 1, 1, want) == 0
+                        assert tuple(got) == tuple(want), (S, n, m16, fin, tuple(got), tuple(want))
+                        R, keep, sharded, one, pre, a_first, late_down, fused, nfused, s0, epi = got
+                        assert (R, keep, sharded, one, epi) == (2 * n, 1, 0, m16, 1)
+                        assert fused == int(fin and S >= 3) and nfused == (fused and (S - 1) // 2 * 2)
+                        assert L.vv_head_m16_active(eng.h, n) == one and L.vv_head_fin_active(eng.h, n) == fused
+        L.vv_head_m16(1)
+        L.vv_head_fin(1)
+        eng.set_steps(3)
+        pos = torch.randn(1, H, generator=g).bfloat16().to(dev)
+        neg = torch.randn(1, H, generator=g).bfloat16().to(dev)
+        noise = torch.randn(2, 64, generator=g).bfloat16()
+        outs = []
+        for _ in range(2):
+            x = noise[:1].to(dev).contiguous()
+            eng.diffusion_sample(pos, neg, x, 1.3)
+            torch.cuda.synchronize()
+            outs.append(x.clone())
+        eng.check_sync()
+        assert torch.equal(outs[0], outs[1]) and bool(torch.isfinite(outs[0].float()).all())
+    finally:
+        L.vv_head_m16(1)
+        L.vv_head_m16_pre(1)
+        L.vv_head_fin(1)
+        eng.close()

@@ -148,6 +148,10 @@ EXPORTS = [
     ("vv_diag_attn_ctx", I, [P, I, I, P, P, P, I, P, P]),
     ("vv_diag_codec_layout", I, [P, I, ctypes.POINTER(I), I]),
     ("vv_diag_codec_state", I, [P, I, I, P, I64]),
+    ("vv_diag_codec_route", I, [I] * 20 + [ctypes.POINTER(I)]),
+    ("vv_diag_codec_plan", I, [P, I, I, ctypes.POINTER(I), I]),
+    ("vv_diag_head_route", I, [I] * 10 + [ctypes.c_longlong, I, I, ctypes.POINTER(I)]),
+    ("vv_diag_head_plan", I, [P, I, ctypes.POINTER(I), I]),
 ]
 
 EPI = {"store": 0, "gelu": 1, "silu_mul": 2, "res": 3, "f32": 4}

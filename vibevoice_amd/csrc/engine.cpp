@@ -620,15 +620,6 @@ extern "C" int vv_codec_stage(int on) {
   g_codec_stage = on & 15;
   return 0;
 }
-static bool codec_stage_any(const ConvNet& net) {
-  for (int i = 0; i < net.nst; ++i)
-    if (codec_stage_fits(net.chans[i], net.T[i], 1, net.depth[i])) return true;
-  return false;
-}
-static bool codec_stage_on(vv_ctx* c, const ConvNet& net, int i, int n) {
-  return g_codec_stage && c->cs_sync.p && codec_stage_fits(net.chans[i], net.T[i], n, net.depth[i]) &&
-         persist_on(c);
-}
 static std::atomic<unsigned long long*> g_codec_stage_stamps{nullptr};
 static std::atomic<int> g_codec_stage_stamp_at{0};
 // diagnostic: the acoustic decoder's stage `stage` records [256][64] per-workgroup phase stamps
@@ -637,10 +628,6 @@ extern "C" int vv_codec_stage_stamps(void* buf, int stage) {
   g_codec_stage_stamp_at = stage;
   return 0;
 }
-extern "C" int vv_codec_stage_active(vv_ctx* c) {
-  return c && c->finalized && codec_stage_on(c, c->dec, 0, 1) ? 1 : 0;
-}
-
 // The narrow stages (C <= 128) as ONE launch each (codec_tile.hip: transition
 // conv + three Block1Ds [+ the decoder's head conv], halo recomputed per
 // workgroup); 0 = k_block per Block1D + the transition GEMMs (A/B and tests).
@@ -656,20 +643,6 @@ extern "C" int vv_codec_tile_stamps(void* buf) {
   g_codec_tile_stamps = (unsigned long long*)buf;
   return 0;
 }
-// the transition fused into stage i's tile launch (CT_PRE_*), or -1: none applies
-static int tile_pre(const ConvNet& net, int i) {
-  const int C = net.chans[i];
-  int pre = CT_PRE_NONE;
-  if (net.decoder && i > 0 && net.rat[i] == 2 && net.chans[i - 1] == 2 * C) pre = CT_PRE_CONVT;
-  if (!net.decoder && i > 0 && net.rat[i] == 2 && 2 * net.chans[i - 1] == C) pre = CT_PRE_SCONV;
-  if (!net.decoder && i == 0 && net.in_ch == 1) pre = CT_PRE_STEM;
-  if (net.decoder && i == 0) return -1;   // (the decoder's stem stage is the widest)
-  const int post = net.decoder && i == net.nst - 1 ? CT_POST_HEAD : CT_POST_NONE;
-  if (!g_codec_tile || !codec_tile_fits(C, pre, post, net.depth[i], net.mix[i].empty() ? 0 : net.mix[i][0].ctx))
-    return -1;
-  return pre;
-}
-
 // The wide stages (C = 256 / 512) as ONE launch each (codec_wide.hip: clusters of
 // C / 32 workgroups per 16-row tile) under the grid-waiting kernels' rule
 // (persist_on: the launch's workgroups must be co-resident); 0 = k_mix + fc1 /
@@ -688,21 +661,89 @@ extern "C" int vv_codec_wide_stamps(void* buf) {   // diagnostic: [n][tiles x S]
   g_codec_wide_stamps = (unsigned long long*)buf;
   return 0;
 }
-// some stage of the net has a wide-stage shape the cluster kernel takes (one sample)
-static bool codec_wide_any(const ConvNet& net) {
-  for (int i = 0; i < net.nst; ++i)
-    if (!net.mix[i].empty() && codec_wide_fits(net.chans[i], net.T[i], 1, net.depth[i], net.mix[i][0].ctx)) return true;
-  return false;
+// ------------------------------------------------------------------ codec plan
+// One StagePlan per stage of a convnet_run call; the routes in priority order (DESIGN.md "How a codec step picks its kernels")
+enum { CR_TILE = 0, CR_WIDE = 1, CR_STAGE = 2, CR_BLOCKS = 3, CR_GEMMS = 4 };
+struct CodecSw { int stage, wide, tile, fusion, persist; };                     // the four switches, persist_on
+struct CodecShape { int decoder, i, nst, C, T, depth, ctx, rat, Cn, in_ch; };   // (Cn: stage i - 1's channels)
+struct CodecFits { bool tile, wide, stage, block, mix; };
+// pre / post: CT_PRE_* / CT_POST_* inside a tile launch; own_pre: the transition before the stage (stage 0: the stem) is
+// a launch of its own; xf_mix (CR_GEMMS): the mixer in fc1's prologue, not k_mix; R (CR_BLOCKS / CR_GEMMS): rows per
+// mixer workgroup (R * C / 8 = 256 conv items: one per thread)
+struct StagePlan { int route, pre, post, own_pre, xf_mix, R; };
+// a plan record of ints as the diag exports' words
+template <class P>
+static int* put_words(const P& p, int* out) {
+  memcpy(out, &p, sizeof(P));
+  return out + sizeof(P) / sizeof(int);
 }
-static bool wide_on(vv_ctx* c, const ConvNet& net, int i, int n) {
-  const int C = net.chans[i];
-  return g_codec_wide && (C == 256 || C == 512) && persist_on(c) && c->cw_sync.p && !net.mix[i].empty() &&
-         codec_wide_fits(C, net.T[i], n, net.depth[i], net.mix[i][0].ctx) && n * ((net.T[i] + 15) / 16) <= pk::CW_LINES;
+static int mixer_rows(int T, int C) { return std::max(1, std::min(T, 2048 / C)); }
+// the transition and the head conv a tile launch of the stage would fuse
+static void codec_tile_ends(const CodecShape& s, int& pre, int& post) {
+  pre = CT_PRE_NONE;
+  if (s.decoder && s.i > 0 && s.rat == 2 && s.Cn == 2 * s.C) pre = CT_PRE_CONVT;
+  if (!s.decoder && s.i > 0 && s.rat == 2 && 2 * s.Cn == s.C) pre = CT_PRE_SCONV;
+  if (!s.decoder && s.i == 0 && s.in_ch == 1) pre = CT_PRE_STEM;
+  post = s.decoder && s.i == s.nst - 1 ? CT_POST_HEAD : CT_POST_NONE;
 }
-extern "C" int vv_codec_wide_active(vv_ctx* c, int n) {   // 1: some acoustic-decoder stage runs it now
-  if (!c || !c->finalized) return 0;
-  for (int i = 0; i < c->dec.nst; ++i)
-    if (wide_on(c, c->dec, i, n)) return 1;
+// The ordering, from plain values (vv_diag_codec_route); f: the five *_fits / *_lds answers at this call's n
+static StagePlan codec_route(const CodecSw& w, const CodecShape& s, const CodecFits& f) {
+  StagePlan p{CR_GEMMS, CT_PRE_NONE, CT_POST_NONE, 1, 0, 0};
+  const bool tile = w.tile && !(s.decoder && s.i == 0) && f.tile;   // (the decoder's stem stage is the widest)
+  p.route = tile ? CR_TILE : w.wide && w.persist && f.wide ? CR_WIDE : w.stage && w.persist && f.stage ? CR_STAGE
+            : (w.fusion & 2) && f.block ? CR_BLOCKS : CR_GEMMS;
+  if (tile) codec_tile_ends(s, p.pre, p.post);
+  p.own_pre = s.i == 0 ? p.pre != CT_PRE_STEM : p.pre != CT_PRE_CONVT && p.pre != CT_PRE_SCONV;
+  p.xf_mix = p.route == CR_GEMMS && (w.fusion & 1) && f.mix;
+  if (p.route >= CR_BLOCKS) p.R = mixer_rows(s.T, s.C);
+  return p;
+}
+extern "C" int vv_diag_codec_route(int stage, int wide, int tile, int fusion, int persist, int decoder, int i, int nst,
+                                   int C, int T, int depth, int ctx, int rat, int Cn, int in_ch, int fit_tile,
+                                   int fit_wide, int fit_stage, int fit_block, int fit_mix, int* out) {
+  if (!out || C < 1) return 1;
+  put_words(codec_route({stage, wide, tile, fusion, persist}, {decoder, i, nst, C, T, depth, ctx, rat, Cn, in_ch},
+                        {fit_tile != 0, fit_wide != 0, fit_stage != 0, fit_block != 0, fit_mix != 0}), out);
+  return 0;
+}
+struct CodecPlan {
+  StagePlan st[VV_MAX_STAGES];
+  int nst;
+  bool own_head() const { return st[nst - 1].post != CT_POST_HEAD; }   // the head conv is a launch of its own
+  bool any(int route) const { return std::any_of(st, st + nst, [&](const StagePlan& p) { return p.route == route; }); }
+  bool grid_waiting() const { return any(CR_STAGE) || any(CR_WIDE); }   // (one sample, ever: vv_finalize's registry count)
+};
+// Per call, not at vv_finalize: the switches and persist_on change between calls (a captured graph replays its capture's
+// plan).  ever: what could run at all -- every switch on, persist_on assumed.  The device-touching part is the five fit
+// answers; the cluster kernel's one sync line per cluster (n x tiles <= pk::CW_LINES) is tested here and nowhere else.
+static CodecPlan codec_plan(vv_ctx* c, const ConvNet& net, int n, bool ever = false) {
+  const CodecSw w = ever ? CodecSw{1, 1, 1, 3, 1}
+                         : CodecSw{g_codec_stage.load(), g_codec_wide.load(), g_codec_tile.load(), g_mix_fusion.load(), persist_on(c)};
+  CodecPlan P{};
+  P.nst = net.nst;
+  for (int i = 0; i < net.nst; ++i) {
+    const int C = net.chans[i], T = net.T[i], depth = net.depth[i], ctx = net.mix[i].empty() ? 0 : net.mix[i][0].ctx;
+    const CodecShape s{net.decoder, i, net.nst, C, T, depth, ctx, net.rat[i], i > 0 ? net.chans[i - 1] : 0, net.in_ch};
+    int pre, post;
+    codec_tile_ends(s, pre, post);
+    P.st[i] = codec_route(w, s, {codec_tile_fits(C, pre, post, depth, ctx),
+                                 n * ((T + 15) / 16) <= pk::CW_LINES && codec_wide_fits(C, T, n, depth, ctx),
+                                 codec_stage_fits(C, T, n, depth), block_lds(mixer_rows(T, C), C) != 0,
+                                 gemv_mix_lds(n * T, T, C) != 0});
+  }
+  return P;
+}
+// test queries: a one-sample step runs the acoustic decoder's stage 0 persistent / an n-sample step some stage of it wide now
+extern "C" int vv_codec_stage_active(vv_ctx* c) { return c && c->finalized && codec_plan(c, c->dec, 1).st[0].route == CR_STAGE; }
+extern "C" int vv_codec_wide_active(vv_ctx* c, int n) { return c && c->finalized && codec_plan(c, c->dec, n).any(CR_WIDE); }
+// diagnostic: the plan of a step of n samples now; out = {nst, own_head, then per stage vv_diag_codec_route's six}
+extern "C" int vv_diag_codec_plan(vv_ctx* c, int net, int n, int* out, int cap) {
+  if (!c || !c->finalized || !out || n < 1 || (net != 0 && net != 1)) FAIL("vv_diag_codec_plan: bad arguments");
+  const CodecPlan P = codec_plan(c, net == 0 ? c->dec : c->sem, n);
+  if (cap < 2 + 6 * P.nst) FAIL("vv_diag_codec_plan: out[] too short (" + std::to_string(2 + 6 * P.nst) + " words)");
+  *out++ = P.nst;
+  *out++ = P.own_head();
+  for (int i = 0; i < P.nst; ++i) out = put_words(P.st[i], out);
   return 0;
 }
 
@@ -718,6 +759,7 @@ struct StageRun {
   float eps;
   RowMap out;   // the last block's output rows: the next transition's input rows, or the head conv's
   hipStream_t st;
+  StagePlan p;
 };
 
 // A Block1D record into the launch-per-block kernels' argument structs
@@ -753,7 +795,7 @@ static MixArgs mix_args(const StageRun& s, int j) {
   mx.n = s.n;
   mx.T = s.T;
   mx.C = s.C;
-  mx.R = std::max(1, std::min(s.T, 2048 / s.C));   // R * C / 8 = 256 conv items: one per thread
+  mx.R = s.p.R;
   mx.eps = s.eps;
   mx.ctx = s.net.mix[s.i][j].ctx;
   mx.slots = s.slots;
@@ -800,18 +842,27 @@ static int convnet_head(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap
   return 0;
 }
 
-// the whole narrow stage in one launch (codec_tile.hip): + the transition `pre`
+// what the tile and the cluster launch's arguments share
+template <class A>
+static A stage_args(const StageRun& s) {
+  A a;
+  memset(&a, 0, sizeof(a));
+  a.n = s.n;
+  a.T = s.T;
+  a.depth = s.net.depth[s.i];
+  a.eps = s.eps;
+  a.slots = s.slots;
+  a.x = s.net.X[s.i];
+  for (int j = 0; j < a.depth; ++j) a.b[j] = s.net.blk[s.i][j];
+  return a;
+}
+
+// the whole narrow stage in one launch (codec_tile.hip): + the transition s.p.pre
 // before it and, with CT_POST_HEAD, the decoder's head conv (-> audio, audio2)
-static int stage_tile(const StageRun& s, int pre, int post, RowMap audio, RowMap audio2) {
+static int stage_tile(const StageRun& s, RowMap audio, RowMap audio2) {
   ConvNet& net = s.net;
-  CodecTileArgs A;
-  memset(&A, 0, sizeof(A));
-  A.n = s.n;
-  A.T = s.T;
-  A.depth = net.depth[s.i];
-  A.eps = s.eps;
-  A.slots = s.slots;
-  A.x = net.X[s.i];
+  const int pre = s.p.pre, post = s.p.post;
+  CodecTileArgs A = stage_args<CodecTileArgs>(s);
   if (pre != CT_PRE_NONE) {
     const bool stem = pre == CT_PRE_STEM;
     const ConvBuf& pb = stem ? net.stem : net.tr[s.i];
@@ -820,7 +871,6 @@ static int stage_tile(const StageRun& s, int pre, int post, RowMap audio, RowMap
     A.pre_w = stem ? net.stem_w : net.tr_w[s.i];
     A.pre_b = stem ? net.stem_b : net.tr_b[s.i];
   }
-  for (int j = 0; j < net.depth[s.i]; ++j) A.b[j] = net.blk[s.i][j];
   if (post == CT_POST_HEAD) {
     A.head_w = net.head_w;
     A.head_b = net.head_b;
@@ -842,15 +892,7 @@ static int stage_tile(const StageRun& s, int pre, int post, RowMap audio, RowMap
 static int stage_wide(vv_ctx* c, const StageRun& s) {
   ConvNet& net = s.net;
   const int C = s.C;
-  CodecWideArgs A;
-  memset(&A, 0, sizeof(A));
-  A.n = s.n;
-  A.T = s.T;
-  A.depth = net.depth[s.i];
-  A.eps = s.eps;
-  A.slots = s.slots;
-  A.x = net.X[s.i];
-  for (int j = 0; j < net.depth[s.i]; ++j) A.b[j] = net.blk[s.i][j];
+  CodecWideArgs A = stage_args<CodecWideArgs>(s);
   A.out = s.out;
   CHK(c->cw_slab.ensure(codec_wide_slab_floats(C, s.T, s.n) * sizeof(float)));
   CHK(c->cw_xbuf.ensure(codec_wide_xbuf_elems(C, s.T, s.n) * sizeof(bf16)));
@@ -920,7 +962,7 @@ static int stage_gemms(vv_ctx* c, const StageRun& s) {
   RowMap Fm = rowmap(net.F, 4LL * C);
   for (int j = 0; j < net.depth[i]; ++j) {
     const Block1D& B = net.blk[i][j];
-    if ((g_mix_fusion & 1) && gemv_mix_lds(n * T, T, C)) {
+    if (s.p.xf_mix) {
       // few rows (T = 1, 8 stages at small batch): the mix runs in fc1's prologue
       GemmArgs g = gemm_args(c, n * T, 4 * C, C, X, B.fc1_w, EPI_GELU, Fm, B.fc1_b);
       g.xf.kind = XF_MIX;
@@ -952,29 +994,22 @@ static int stage_gemms(vv_ctx* c, const StageRun& s) {
 // in `stem` (rows [ctx, ctx+T0)).  Decoder: writes audio to out (+ out2).
 // Encoder: writes [n, out_ch] features to out.
 static int convnet_run(vv_ctx* c, ConvNet& net, int n, const int* slots, RowMap out, RowMap out2, hipStream_t st) {
-  // (the encoders' stem is fused into stage 0's tile launch where it applies)
-  if (net.decoder || tile_pre(net, 0) != CT_PRE_STEM) CHK(convnet_stem(c, net, n, slots, st));
-  bool head_done = false;
+  const CodecPlan P = codec_plan(c, net, n);
   for (int i = 0; i < net.nst; ++i) {
-    const int T = net.T[i], C = net.chans[i];
-    const int tpre = tile_pre(net, i);
-    if (i > 0 && tpre != CT_PRE_CONVT && tpre != CT_PRE_SCONV) CHK(convnet_transition(c, net, i, n, slots, st));
+    const StagePlan& p = P.st[i];
+    // (the encoders' stem and the 2x transitions are fused into the stage's tile launch where it applies)
+    if (p.own_pre) CHK(i == 0 ? convnet_stem(c, net, n, slots, st) : convnet_transition(c, net, i, n, slots, st));
     const ConvBuf& nb = (i + 1 < net.nst) ? net.tr[i + 1] : net.head;
-    const StageRun s{net, i, n, T, C, slots, c->cfg.codec_eps, buf_in_rows(nb, T, slots), st};
-    if (tpre >= 0) {
-      head_done = net.decoder && i == net.nst - 1;
-      CHK(stage_tile(s, tpre, head_done ? CT_POST_HEAD : CT_POST_NONE, out, out2));
-    } else if (wide_on(c, net, i, n)) {
-      CHK(stage_wide(c, s));
-    } else if (codec_stage_on(c, net, i, n)) {
-      CHK(stage_persistent(c, s));
-    } else if ((g_mix_fusion & 2) && block_lds(std::max(1, std::min(T, 2048 / C)), C)) {
-      CHK(stage_blocks(s));
-    } else {
-      CHK(stage_gemms(c, s));
+    const StageRun s{net, i, n, net.T[i], net.chans[i], slots, c->cfg.codec_eps, buf_in_rows(nb, net.T[i], slots), st, p};
+    switch (p.route) {
+      case CR_TILE: CHK(stage_tile(s, out, out2)); break;
+      case CR_WIDE: CHK(stage_wide(c, s)); break;
+      case CR_STAGE: CHK(stage_persistent(c, s)); break;
+      case CR_BLOCKS: CHK(stage_blocks(s)); break;
+      default: CHK(stage_gemms(c, s));
     }
   }
-  if (!head_done) CHK(convnet_head(c, net, n, slots, out, out2, st));
+  if (P.own_head()) CHK(convnet_head(c, net, n, slots, out, out2, st));
   return 0;
 }
 
@@ -1263,8 +1298,7 @@ int vv_finalize(vv_ctx* c) {
     CHK(c->m16_buf.ensure(16 * 192 * sizeof(float) + 16 * (size_t)k.hidden * sizeof(bf16)));
     HIPCHK(hipMemset(c->m16_buf.p, 0, 16 * 192 * sizeof(float)));
   }
-  c->persist_capable = codec_stage_any(c->dec) || codec_stage_any(c->sem) || codec_wide_any(c->dec) ||
-                       codec_wide_any(c->sem) ||
+  c->persist_capable = codec_plan(c, c->dec, 1, true).grid_waiting() || codec_plan(c, c->sem, 1, true).grid_waiting() ||
                        (c->head_gemv && head_m16_fits(k.hidden, k.head_ffn, 16)) ||
                        lf_fits || lf16_fits || la_fits;
   if (c->persist_ok && !c->persist_follow && c->persist_capable && !c->hl_registered) {
@@ -2014,16 +2048,98 @@ extern "C" int vv_diag_sync_words(vv_ctx* c, unsigned* out, int n) {
 }
 
 // ------------------------------------------------------------------ diffusion head
-// One rank's buffers and operands of a vv_diffusion_sample call.
+// 2n <= 16 rows in the GEMV layout: the layer as one launch (head_m16.hip) while the context is
+// the device's only registered one; 0 = two GEMV launches (A/B and tests)
+static std::atomic<int> g_head_m16{1};
+extern "C" int vv_head_m16(int on) {
+  g_head_m16 = on;   // A/B variants: bit 1 / bit 3 HeadM16Args::a_first on / off (default: > 8 rows),
+                     // bit 2 the down weights' earlier issue point
+  return 0;
+}
+// layers l >= 1 build the A side distributed (HeadM16Args::pre) from the previous
+// layer's row partials; 0 = every workgroup transforms the whole A side
+static std::atomic<int> g_head_m16_pre{1};
+extern "C" int vv_head_m16_pre(int on) {
+  g_head_m16_pre = on;
+  return 0;
+}
+static std::atomic<unsigned long long*> g_head_m16_stamps{nullptr};
+extern "C" int vv_head_m16_stamps(void* buf) {   // diagnostic: [256][16] per-workgroup phase stamps
+  g_head_m16_stamps = (unsigned long long*)buf;
+  return 0;
+}
+// step s's final layer + DPM and step s + 1's noisy projection as ONE launch
+// (head_fin.hip) at 2n <= 16 rows with the head's weights cache-resident; 0 = the
+// two launches (A/B and tests)
+static std::atomic<int> g_head_fin{1};
+extern "C" int vv_head_fin(int on) {
+  g_head_fin = on ? 1 : 0;
+  return 0;
+}
+
+// One record per vv_diffusion_sample call (DESIGN.md "How a diffusion sample picks its kernels"), all ints:
+// vv_diag_head_route's words.  R: 2n rows.  keep: the per-step head weights (noisy, gate|up, down, final: 170 MB at
+// 1.5B) are re-read by every diffusion step: default cache policy keeps them in the Infinity Cache (256 MB) across the
+// S steps; VibeVoice-Large's (925 MB per step; 231 MB per rank at TP = 4) stream non-temporal like the LM's.
+// sharded: x is summed over the ranks after every layer.  m16: a layer is one k_head_m16 launch, with pre (the A side
+// built distributed above 4 rows, the noisy projection then k_head_noisy16: at 2 - 4 rows the whole A side is 18 - 36
+// KB per CU and the extra grid wait costs more than it saves, n = 1 head sample 659 us whole vs 688 us distributed),
+// a_first (the A side ahead of every weight load: at 16 rows a whole head sample 890 -> 860 us, at 2 rows 595 -> 603
+// us; tools/head_m16_stamps.py) and late_down.  fin: k_head_fin fuses step s's final layer with step s + 1's noisy
+// projection for an EVEN number nfused of steps [s0, S - 1), so that the latents, the DPM history and the state rows
+// ping-pong back to x_io / m1 / xh for the last step's final layer.  epi_dpm: CFG + DPM is the final GEMM's epilogue.
+struct HeadPlan { int R, keep, sharded, m16, pre, a_first, late_down, fin, nfused, s0, epi_dpm; };
+// The rule, from plain values (vv_diag_head_route): the three switches (one snapshot each), wbytes the head layers'
+// weight bytes, fit_* the answers of head_m16_fits and head_fin_fits at R rows.
+static HeadPlan head_route(int head_tp, int head_gemv, int tp_size, int comm, int m16, int m16_pre, int fin, int persist,
+                           int steps, int R, long long wbytes, bool fit_m16, bool fit_fin) {
+  HeadPlan p{};
+  p.R = R;
+  p.keep = wbytes <= (192ll << 20) && !(head_tp && tp_size > 1);
+  p.sharded = head_tp && (tp_size > 1 || comm);   // (a 1-rank communicator: tests)
+  p.m16 = m16 && !head_tp && head_gemv && fit_m16 && persist;
+  p.pre = m16_pre && R > 4 && p.m16;
+  p.a_first = (m16 & 2) ? 1 : (m16 & 8) ? 0 : R > 8;
+  p.late_down = !(m16 & 4);
+  p.fin = fin && !head_tp && p.keep && fit_fin && steps >= 3;
+  p.nfused = !p.fin ? 0 : (steps - 1) % 2 == 0 ? steps - 1 : steps - 2;
+  p.s0 = steps - 1 - p.nfused;
+  p.epi_dpm = R <= 16;
+  return p;
+}
+extern "C" int vv_diag_head_route(int head_tp, int head_gemv, int tp_size, int comm, int m16, int m16_pre, int fin,
+                                  int persist, int steps, int R, long long wbytes, int fit_m16, int fit_fin, int* out) {
+  if (!out) return 1;
+  put_words(head_route(head_tp, head_gemv, tp_size, comm, m16, m16_pre, fin, persist, steps, R, wbytes, fit_m16 != 0,
+                       fit_fin != 0), out);
+  return 0;
+}
+static HeadPlan head_plan(vv_ctx* c, int n) {
+  const vv_config& k = c->cfg;
+  return head_route(c->head_tp, c->head_gemv, c->tp_size, c->comm != nullptr, g_head_m16.load(), g_head_m16_pre.load(),
+                    g_head_fin.load(), persist_on(c), c->steps, 2 * n,
+                    (long long)k.head_layers * 3 * k.head_ffn * k.hidden * sizeof(bf16),
+                    head_m16_fits(k.hidden, k.head_ffn, 2 * n), head_fin_fits(k.hidden, k.latent_dim, 2 * n));
+}
+// test queries: a sample of n rows on c would run k_head_m16 / k_head_fin now; diagnostic: head_plan's eleven words
+extern "C" int vv_head_m16_active(vv_ctx* c, int n) { return c && c->finalized && head_plan(c, n).m16 ? 1 : 0; }
+extern "C" int vv_head_fin_active(vv_ctx* c, int n) { return c && c->finalized && head_plan(c, n).fin ? 1 : 0; }
+extern "C" int vv_diag_head_plan(vv_ctx* c, int n, int* out, int cap) {
+  if (!c || !c->finalized || !out || n < 1 || cap < 11) FAIL("vv_diag_head_plan: bad arguments");
+  put_words(head_plan(c, n), out);
+  return 0;
+}
+
+// One rank's plan, buffers and operands of a vv_diffusion_sample call.
 struct HeadRun {
-  int n = 0, R = 0;
+  HeadPlan p{};
+  int n = 0;
   long long MODW = 0;
   bf16 *cat = nullptr, *condp = nullptr, *xh = nullptr, *mods = nullptr, *sa = nullptr, *act = nullptr, *v = nullptr,
        *m1 = nullptr;
   bf16 *xh2 = nullptr, *lat2 = nullptr, *m12 = nullptr;   // k_head_fin's double buffers (state rows, latents, history)
   const bf16* cond = nullptr;
   RowMap xh_m;
-  bool keep = false;
 };
 
 // layout, condition rows and cond_proj (step-invariant: once per token)
@@ -2031,9 +2147,8 @@ static int head_begin(vv_ctx* c, int n, const void* pos_h, const void* neg_h, He
   const vv_config& k = c->cfg;
   const int H = k.hidden, F = k.head_ffn, D = k.latent_dim, L = k.head_layers;
   h.n = n;
-  h.R = 2 * n;
   h.MODW = (3LL * L + 2) * H;
-  const int R = h.R;
+  const int R = h.p.R;
   h.cat = (bf16*)c->head_ws.p;
   h.condp = h.cat + (size_t)R * H;
   bf16* sc = h.condp + (size_t)R * H;
@@ -2055,17 +2170,12 @@ static int head_begin(vv_ctx* c, int n, const void* pos_h, const void* neg_h, He
     HIPCHK(hipMemcpyAsync(h.cat + (size_t)n * H, neg_h, (size_t)n * H * sizeof(bf16), hipMemcpyDeviceToDevice, st));
     h.cond = h.cat;
   }
-  // the per-step head weights (noisy, gate|up, down, final: 170 MB at 1.5B) are
-  // re-read by every diffusion step: default cache policy keeps them in the
-  // Infinity Cache (256 MB) across the S steps.  VibeVoice-Large's (925 MB per
-  // step; 231 MB per rank at TP = 4) stream non-temporal like the LM's
-  h.keep = (size_t)L * 3 * F * H * sizeof(bf16) <= (192ull << 20) && !(c->head_tp && c->tp_size > 1);
   CHK(gemm(c, gemm_args(c, R, H, H, rowmap(h.cond, H), c->head.cond, EPI_STORE, rowmap(h.condp, H)), st));
   return 0;
 }
 
 static int head_gemm(vv_ctx* c, const HeadRun& h, GemmArgs g, hipStream_t st) {
-  g.keep = h.keep ? 1 : 0;
+  g.keep = h.p.keep;
   return gemm(c, g, st);
 }
 
@@ -2076,71 +2186,32 @@ static int head_gemm(vv_ctx* c, const HeadRun& h, GemmArgs g, hipStream_t st) {
 static int head_mods(vv_ctx* c, const HeadRun& h, int s, hipStream_t st) {
   if (s % HEAD_SC) return 0;
   const int H = c->cfg.hidden, sc = std::min(HEAD_SC, c->steps - s);
-  KCHK(launch_head_cond(sc, h.R, H, h.condp, (const bf16*)c->temb.p + (size_t)s * H, h.sa, st));
-  CHK(gemm(c, gemm_args(c, sc * h.R, (int)h.MODW, H, rowmap(h.sa, H), c->head.ada, EPI_STORE,
+  KCHK(launch_head_cond(sc, h.p.R, H, h.condp, (const bf16*)c->temb.p + (size_t)s * H, h.sa, st));
+  CHK(gemm(c, gemm_args(c, sc * h.p.R, (int)h.MODW, H, rowmap(h.sa, H), c->head.ada, EPI_STORE,
                         rowmap(h.mods, h.MODW)), st));
   return 0;
 }
 
-// 2n <= 16 rows in the GEMV layout: the layer as one launch (head_m16.hip) while the context is
-// the device's only registered one; 0 = two GEMV launches (A/B and tests)
-static std::atomic<int> g_head_m16{1};
-// layers l >= 1 build the A side distributed (HeadM16Args::pre) from the previous
-// layer's row partials; 0 = every workgroup transforms the whole A side
-static std::atomic<int> g_head_m16_pre{1};
-extern "C" int vv_head_m16_pre(int on) {
-  g_head_m16_pre = on;
-  return 0;
-}
-static std::atomic<unsigned long long*> g_head_m16_stamps{nullptr};
-extern "C" int vv_head_m16_stamps(void* buf) {   // diagnostic: [256][16] per-workgroup phase stamps
-  g_head_m16_stamps = (unsigned long long*)buf;
-  return 0;
-}
-extern "C" int vv_head_m16(int on) {
-  g_head_m16 = on;   // A/B variants: bit 1 / bit 3 HeadM16Args::a_first on / off (default: > 8 rows),
-                     // bit 2 the down weights' earlier issue point
-  return 0;
-}
-// the one-launch layer applies (R <= 16 rows, GEMV layout, unsharded, sole context)
-static bool m16_on(vv_ctx* c, int R) {
-  return g_head_m16 && !c->head_tp && c->head_gemv && c->m16_buf.p && head_m16_fits(c->cfg.hidden, c->cfg.head_ffn, R) &&
-         persist_on(c);
-}
-
-// ... with the A side built distributed (HeadM16Args::pre) above 4 rows: at 2 -
-// 4 rows the whole A side is 18 - 36 KB per CU and the extra grid wait costs more
-// than it saves (n = 1 head sample 659 us whole vs 688 us distributed,
-// tools/head_m16_stamps.py)
-static bool m16_pre(vv_ctx* c, int R) { return g_head_m16_pre && R > 4 && m16_on(c, R); }
-
 // x = noisy_images_proj(cat[x, x])  -- both halves read the same n latent rows
 static int head_noisy(vv_ctx* c, const HeadRun& h, const void* x_io, hipStream_t st) {
   const int H = c->cfg.hidden, D = c->cfg.latent_dim;
-  if (m16_pre(c, h.R)) {   // + the row partials layer 0's distributed A side reads
+  if (h.p.pre) {   // k_head_noisy16: + the row partials layer 0's distributed A side reads
     HeadNoisyArgs a;
     a.lat = (const bf16*)x_io;
     a.w = c->head.noisy;
     a.x = (bf16*)h.xh;
     a.ssp = (float*)c->m16_buf.p;
     a.n = h.n;
-    a.R = h.R;
+    a.R = h.p.R;
     a.D = D;
     a.ldx = H;
     KCHK(launch_head_noisy16(a, st));
     return 0;
   }
-  return head_gemm(c, h, gemm_args(c, h.R, H, D, rowmap(x_io, D, h.n, 0), c->head.noisy, EPI_STORE, h.xh_m),
+  return head_gemm(c, h, gemm_args(c, h.p.R, H, D, rowmap(x_io, D, h.n, 0), c->head.noisy, EPI_STORE, h.xh_m),
                    st);
 }
 
-extern "C" int vv_head_m16_active(vv_ctx* c, int n) {
-  const vv_config& k = c->cfg;
-  return c && c->finalized && g_head_m16 && !c->head_tp && c->head_gemv && head_m16_fits(k.hidden, k.head_ffn, 2 * n) &&
-                 persist_on(c)
-             ? 1
-             : 0;
-}
 // layer l of step s: modulate(norm(x)) -> gate|up -> SiLU*up -> down -> x += gate * (.)
 // With the FFN sharded (vv_tp_shard_head) this rank holds head_ffn / tp_size of
 // the hidden columns: gate|up column-parallel, down row-parallel; rank 0 adds
@@ -2150,13 +2221,13 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
   const vv_config& k = c->cfg;
   const int H = k.hidden, F = k.head_ffn;
   const HeadLayerW& w = c->headw[l];
-  const bf16* mod = h.mods + (size_t)(s % HEAD_SC) * h.R * h.MODW;
+  const bf16* mod = h.mods + (size_t)(s % HEAD_SC) * h.p.R * h.MODW;
   const int o = 3 * H * l;
   // modulate(norm(x), shift, scale) fused into gate|up's A load
-  GemmArgs g = gemm_args(c, h.R, 2 * F, H, h.xh_m, w.gu, EPI_SILU_MUL, rowmap(h.act, F));
+  GemmArgs g = gemm_args(c, h.p.R, 2 * F, H, h.xh_m, w.gu, EPI_SILU_MUL, rowmap(h.act, F));
   g.xf = xf_norm(w.norm, k.head_eps, mod, h.MODW, o, o + H);
   const bool partial = c->head_tp && c->tp_size > 1 && c->tp_rank > 0;
-  if (m16_on(c, h.R)) {
+  if (h.p.m16) {
     // 2n <= 16 rows, GEMV layout: one launch with two grid-wide waits (head_m16.hip)
     HeadM16Args a;
     memset(&a, 0, sizeof(a));
@@ -2168,7 +2239,7 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
     a.shift_off = o;
     a.scale_off = o + H;
     a.gate_off = o + 2 * H;
-    a.R = h.R;
+    a.R = h.p.R;
     a.eps = k.head_eps;
     a.nw = w.norm;
     a.gu = w.gu;
@@ -2177,21 +2248,19 @@ static int head_layer(vv_ctx* c, const HeadRun& h, int s, int l, hipStream_t st)
     a.sync = (unsigned*)c->hf_sync.p;
     a.err = err_word(c);
     a.stamps = g_head_m16_stamps;
-    // the A side ahead of every weight load: at 16 rows (B = 8) a whole head
-    // sample 890 -> 860 us, at 2 rows (B = 1) 595 -> 603 us (tools/head_m16_stamps.py)
-    a.a_first = (g_head_m16.load() & 2) ? 1 : (g_head_m16.load() & 8) ? 0 : (h.R > 8 ? 1 : 0);
-    a.late_down = (g_head_m16.load() & 4) ? 0 : 1;
+    a.a_first = h.p.a_first;
+    a.late_down = h.p.late_down;
     a.ssp = (float*)c->m16_buf.p;
     a.xt = (bf16*)((char*)c->m16_buf.p + 16 * 192 * sizeof(float));
-    a.pre = m16_pre(c, h.R) ? 1 : 0;   // (layer 0: the partials of k_head_noisy16)
+    a.pre = h.p.pre;   // (layer 0: the partials of k_head_noisy16)
     KCHK(launch_head_m16(a, st));
     return 0;
   }
   if (!c->head_gemv)
-    FAIL("diffusion head: " + std::to_string(h.R) + " rows need the GEMV layout (head.<l>.gu_w / down_w), which this "
+    FAIL("diffusion head: " + std::to_string(h.p.R) + " rows need the GEMV layout (head.<l>.gu_w / down_w), which this "
          "engine did not bind");
   CHK(head_gemm(c, h, g, st));
-  g = gemm_args(c, h.R, H, F, rowmap(h.act, F), w.down, EPI_RES, h.xh_m);
+  g = gemm_args(c, h.p.R, H, F, rowmap(h.act, F), w.down, EPI_RES, h.xh_m);
   g.epi.res = partial ? rowmap(c->zero_rows.p, H) : h.xh_m;
   g.epi.gate = rowmap(mod + o + 2 * H, h.MODW);
   return head_gemm(c, h, g, st);
@@ -2202,14 +2271,14 @@ static int head_final(vv_ctx* c, const HeadRun& h, int s, void* x_io, float cfg_
                       hipStream_t st) {
   const vv_config& k = c->cfg;
   const int H = k.hidden, D = k.latent_dim, L = k.head_layers;
-  const bf16* mod = h.mods + (size_t)(s % HEAD_SC) * h.R * h.MODW;
+  const bf16* mod = h.mods + (size_t)(s % HEAD_SC) * h.p.R * h.MODW;
   DpmCoef e = c->coef[s];
   e.cfg = cfg_scale;
   // sde-dpmsolver++: this step's [2n, D] fp32 draw; rows [0, n) update the live latents
-  const float* zs = sde_noise ? sde_noise + (size_t)s * h.R * D : nullptr;
-  GemmArgs g = gemm_args(c, h.R, D, H, h.xh_m, c->head.final, EPI_STORE, rowmap(h.v, D));
+  const float* zs = sde_noise ? sde_noise + (size_t)s * h.p.R * D : nullptr;
+  GemmArgs g = gemm_args(c, h.p.R, D, H, h.xh_m, c->head.final, EPI_STORE, rowmap(h.v, D));
   g.xf = xf_norm(nullptr, k.head_eps, mod, h.MODW, 3 * H * L, 3 * H * L + H);
-  if (h.R <= 16) {
+  if (h.p.epi_dpm) {
     g.epi.kind = EPI_CFG_DPM;
     g.dpm.n = h.n;
     g.dpm.k = e;
@@ -2233,8 +2302,9 @@ extern "C" int vv_head_layers_replay(vv_ctx* c, int n, const void* pos_h, const 
   hipStream_t st = (hipStream_t)vst;
   if (!c->finalized || c->steps == 0) FAIL("vv_head_layers_replay: engine not finalized or no schedule");
   if (n <= 0 || n > c->cfg.max_batch) FAIL("vv_head_layers_replay: bad n");
-  if (c->head_tp && (c->tp_size > 1 || c->comm)) FAIL("vv_head_layers_replay: sharded head");
   HeadRun h;
+  h.p = head_plan(c, n);
+  if (h.p.sharded) FAIL("vv_head_layers_replay: sharded head");
   CHK(head_begin(c, n, pos_h, neg_h, h, st));
   CHK(head_mods(c, h, 0, st));
   for (int r = 0; r < reps; ++r)
@@ -2248,27 +2318,6 @@ int vv_tp_shard_head(vv_ctx* c, int on) {
   return 0;
 }
 
-// step s's final layer + DPM and step s + 1's noisy projection as ONE launch
-// (head_fin.hip) at 2n <= 16 rows with the head's weights cache-resident; 0 = the
-// two launches (A/B and tests)
-static std::atomic<int> g_head_fin{1};
-extern "C" int vv_head_fin(int on) {
-  g_head_fin = on ? 1 : 0;
-  return 0;
-}
-static bool head_fin_on(vv_ctx* c, const HeadRun& h) {
-  const vv_config& k = c->cfg;
-  return g_head_fin && !c->head_tp && h.keep && head_fin_fits(k.hidden, k.latent_dim, h.R) && c->steps >= 3;
-}
-extern "C" int vv_head_fin_active(vv_ctx* c, int n) {
-  if (!c || !c->finalized) return 0;
-  HeadRun h;
-  h.n = n;
-  h.R = 2 * n;
-  const vv_config& k = c->cfg;
-  h.keep = (size_t)k.head_layers * 3 * k.head_ffn * k.hidden * sizeof(bf16) <= (192ull << 20) && !(c->head_tp && c->tp_size > 1);
-  return head_fin_on(c, h) ? 1 : 0;
-}
 // lat / m1 read, lat_out / m1_out written; the state rows h.xh read, xo written
 static int head_fin(vv_ctx* c, const HeadRun& h, int s, const bf16* lat, bf16* lat_out, const bf16* m1, bf16* m1_out,
                     bf16* xo, float cfg_scale, const float* sde_noise, hipStream_t st) {
@@ -2277,13 +2326,13 @@ static int head_fin(vv_ctx* c, const HeadRun& h, int s, const bf16* lat, bf16* l
   HeadFinArgs a;
   memset(&a, 0, sizeof(a));
   a.n = h.n;
-  a.R = h.R;
+  a.R = h.p.R;
   a.eps = k.head_eps;
   a.shift_off = 3 * H * L;
   a.scale_off = 3 * H * L + H;
   a.ldmod = h.MODW;
   a.x = h.xh;
-  a.mod = h.mods + (size_t)(s % HEAD_SC) * h.R * h.MODW;
+  a.mod = h.mods + (size_t)(s % HEAD_SC) * h.p.R * h.MODW;
   a.fw = c->head.final;
   a.k = c->coef[s];
   a.k.cfg = cfg_scale;
@@ -2291,10 +2340,10 @@ static int head_fin(vv_ctx* c, const HeadRun& h, int s, const bf16* lat, bf16* l
   a.lat_out = lat_out;
   a.m1 = m1;
   a.m1_out = m1_out;
-  a.noise = sde_noise ? sde_noise + (size_t)s * h.R * D : nullptr;
+  a.noise = sde_noise ? sde_noise + (size_t)s * h.p.R * D : nullptr;
   a.nw = c->head.noisy;
   a.xo = xo;
-  a.ssp = m16_pre(c, h.R) ? (float*)c->m16_buf.p : nullptr;   // (layer 0's distributed A side at > 4 rows)
+  a.ssp = h.p.pre ? (float*)c->m16_buf.p : nullptr;   // (layer 0's distributed A side at > 4 rows)
   KCHK(launch_head_fin(a, st));
   return 0;
 }
@@ -2306,21 +2355,14 @@ int vv_diffusion_sample(vv_ctx* c, int n, const void* pos_h, const void* neg_h, 
   if (n <= 0) return 0;
   const vv_config& k = c->cfg;
   if (n > k.max_batch) FAIL("vv_diffusion_sample: n > max_batch");
-  const bool sharded = c->head_tp && (c->tp_size > 1 || c->comm);   // (a 1-rank communicator: tests)
-  if (sharded && !c->comm) FAIL("sharded diffusion head without a communicator (vv_tp_init; one process: "
-                                "vv_diffusion_sample_group)");
-  const int H = k.hidden, D = k.latent_dim, L = k.head_layers;
+  const int H = k.hidden, L = k.head_layers;
   HeadRun h;
+  h.p = head_plan(c, n);
+  const bool sharded = h.p.sharded;
+  if (sharded && !c->comm)
+    FAIL("sharded diffusion head without a communicator (vv_tp_init; one process: vv_diffusion_sample_group)");
   CHK(head_begin(c, n, pos_h, neg_h, h, st));
-  const int R = h.R;
-  const long long MODW = h.MODW;
-  // k_head_fin fuses step s's final layer with step s + 1's noisy projection for
-  // an EVEN number of steps [s0, S - 1), so that the latents, the DPM history and
-  // the state rows ping-pong back to x_io / m1 / xh for the last step's final
-  // layer (the GEMV path, in place)
-  const bool fin = !sharded && head_fin_on(c, h);
-  const int nfused = !fin ? 0 : (c->steps - 1) % 2 == 0 ? c->steps - 1 : c->steps - 2;
-  const int s0 = c->steps - 1 - nfused;
+  const int R = h.p.R, nfused = h.p.nfused, s0 = h.p.s0;
   bf16* lat[2] = {(bf16*)x_io, h.lat2};
   bf16* hist[2] = {h.m1, h.m12};
   bf16* xs[2] = {h.xh, h.xh2};
@@ -2363,11 +2405,12 @@ int vv_diffusion_sample_group(int nr, vv_ctx* const* ctxs, int n, const void* po
       FAIL("vv_diffusion_sample_group: engine r must be TP rank r of n with a sharded head (vv_tp_shard_head)");
     if (!c->finalized || c->steps != ctxs[0]->steps) FAIL("vv_diffusion_sample_group: engines not finalized alike");
     if (n > c->cfg.max_batch) FAIL("vv_diffusion_sample_group: n > max_batch");
+    h[r].p = head_plan(c, n);
     CHK(head_begin(c, n, pos_h, neg_h, h[r], st));
     sr.p[r] = h[r].xh;
   }
   const vv_config& k = ctxs[0]->cfg;
-  const long long count = (long long)h[0].R * k.hidden;
+  const long long count = (long long)h[0].p.R * k.hidden;
   for (int s = 0; s < ctxs[0]->steps; ++s) {
     for (int r = 0; r < nr; ++r) {
       CHK(head_mods(ctxs[r], h[r], s, st));
