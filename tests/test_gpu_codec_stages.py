@@ -387,6 +387,70 @@ def test_form_hand_over(G):
         eng.close()
 
 
+def test_first_block_norm_rows_same_bits_in_every_form(G):
+    """The mixer norm is one rounding chain for every kernel form (csrc/codec_dev.h: cb_ss8, the form's row sum,
+    cb_norm).  Block 0's mixer history rows of a stage are norm(x) of the stage input and depend on nothing else
+    (no fc1, GELU or fc2), so with the stage input held fixed they must agree bit for bit between the forms.  From a
+    reset state one frame of slot 0 is run per arm, each arm with one switch away from the default; the stages
+    upstream of the one compared run the same kernels in both runs, and the compared stage's input rows (the rows
+    its transition buffer holds) are asserted equal first, so a failure says which side moved.
+      dec stage 0 (C = 2,048, T = 1): persistent stage | XF_MIX GEMV (vv_codec_stage 0) | k_mix (+ mix fusion 0)
+      dec stage 2 (C = 512, T = 40):  wide clusters | k_mix + GEMM (vv_codec_wide 0)
+      dec stage 4 (C = 128, T = 400): tile | k_block (vv_codec_tile 0)
+    Rows compared: only the last min(T, 6) of this frame's rows [ctx, ctx + T) -- 1 of 1, 6 of 40 and 6 of 400 --
+    the rows the next frame reads; the one-launch forms store no others (include/vibevoice_hip_diag.h,
+    vv_diag_codec_state), so the earlier rows of a frame are pinned only through the stage tests above.
+    On the commit before codec_dev.h every pair was already exact (0 differing values of 2,048 / 3,072 / 768 in
+    the three stages, k_mix arm included): all four pairs assert torch.equal."""
+    L = _lib.lib()
+    eng, lay = make_engine(G)
+    lat = torch.randn(1, 64, generator=torch.Generator().manual_seed(61)).bfloat16()
+    ne = cr.layout_elems(lay[0])
+
+    def run(stage=1, wide=1, tile=1, fusion=3):
+        L.vv_codec_stage(stage)
+        L.vv_codec_wide(wide)
+        L.vv_codec_tile(tile)
+        L.vv_codec_mix_fusion(fusion)
+        eng.codec_reset(torch.arange(NSLOT, dtype=torch.int32, device=dev))
+        step(eng, G, [0], lat)
+        t = torch.empty(ne, dtype=torch.bfloat16, device=dev)
+        _lib.check(L.vv_diag_codec_state(eng.h, 0, 0, ctypes.c_void_p(t.data_ptr()), ne), "diag_codec_state")
+        w = (ctypes.c_int * 64)()
+        _lib.check(L.vv_diag_codec_plan(eng.h, 0, 1, w, 64), "diag_codec_plan")
+        return cr.split_dump(t.cpu(), lay[0]), [w[2 + 6 * i] for i in range(7)], [w[6 + 6 * i] for i in range(7)]
+
+    def rows(bufs, i):
+        b_in = lay[0][cr.find_buf(lay[0], "decoder", cr.pre_key("decoder", i))]
+        b_mx = lay[0][cr.find_buf(lay[0], "decoder", cr.mixer_key("decoder", i, 0))]
+        x = bufs[lay[0].index(b_in)][b_in["ctx"]: b_in["ctx"] + b_in["T"]]
+        T, c = b_mx["T"], b_mx["ctx"]
+        return x, bufs[lay[0].index(b_mx)][c + max(T - 6, 0): c + T]
+
+    try:
+        base, route, _ = run()
+        assert (route[0], route[2], route[4]) == (STAGE, WIDE, TILE), route
+        arms = [("stage|xf_mix", 0, dict(stage=0), GEMMS, 1), ("stage|k_mix", 0, dict(stage=0, fusion=0), GEMMS, 0),
+                ("wide|k_mix", 2, dict(wide=0), GEMMS, 0), ("tile|k_block", 4, dict(tile=0), BLOCKS, 0)]
+        for name, i, kw, want_route, want_xf in arms:
+            other, route, xf = run(**kw)
+            assert (route[i], xf[i]) == (want_route, want_xf), (name, route, xf)
+            (xa, na), (xb, nb) = rows(base, i), rows(other, i)
+            assert na.abs().sum() > 0 and na.shape == nb.shape and na.shape[0] == min(6, lay[0][cr.find_buf(
+                lay[0], "decoder", cr.mixer_key("decoder", i, 0))]["T"])
+            print(f"{name}: stage {i} input values that differ {int((xa != xb).sum())} of {xa.numel()}, "
+                  f"norm rows {int((na != nb).sum())} of {na.numel()}")
+            assert torch.equal(xa, xb), (name, "the stage input moved")
+            assert torch.equal(na, nb), (name, "block 0's mixer norm rows differ")
+        eng.check_sync()
+    finally:
+        L.vv_codec_stage(1)
+        L.vv_codec_wide(1)
+        L.vv_codec_tile(1)
+        L.vv_codec_mix_fusion(3)
+        eng.close()
+
+
 def test_diag_state_rejects_short_capacity(G):
     eng, lay = make_engine(G)
     try:

@@ -1,10 +1,5 @@
-// σ-VAE codec Block1D (modular_vibevoice_tokenizer.py:667-684, streaming conv
-// :327-382) on the streaming decode path:
-//   n_t = ConvRMSNorm(x_t)                        -> conv buffer (next steps' history)
-//   y_t = x_t + bf16(bf16(dwconv_k7(n)_t + b) * gamma)
-//   a_t = ConvRMSNorm_ffn(y_t)
-//   out_t = y_t + bf16(ffn_gamma * bf16(fc2(GELU(fc1(a_t)))))
-//
+// σ-VAE codec Block1D on the streaming decode path, one launch per block or per
+// half block (the formula and its element arithmetic: codec_dev.h):
 //   k_mix   : the front half (n, y, a) for any C <= 2048; fc1 / fc2 then run as
 //             GEMMs (gemm.hip), or fc1 takes the mix in its prologue (XF_MIX)
 //   k_block : the whole block in one workgroup for the narrow stages
@@ -12,7 +7,7 @@
 //             MFMA with the weights read from L2 and the hidden rows in LDS.
 //             Same arithmetic and summation order as k_mix + k_gemm (one fp32
 //             accumulator per output, 32-wide K chunks in order): bit-identical.
-#include "kernels.h"
+#include "codec_dev.h"
 
 // ---------------------------------------------------------------- front half
 // A workgroup owns rows [t0, t0 + R) of one sample and all C channels; it
@@ -25,7 +20,7 @@
 // LDS: nrm [R + ctx][C] | ybuf [R][C] | ssp [R + ctx][C/8] | inv [R + ctx].
 // TO_LDS: fc1's input rows go to a_lds (row stride a_ld) instead of a.a, and y
 // is not stored to a.y (k_block keeps the residual in ybuf).
-DEV size_t mix_lds_bytes(int R, int ctx, int C) {
+__host__ __device__ inline size_t mix_lds_bytes(int R, int ctx, int C) {
   return (size_t)(2 * R + ctx) * C * sizeof(bf16) + (size_t)(R + ctx) * (C / 8 + 1) * sizeof(float);
 }
 
@@ -86,12 +81,7 @@ DEV void mix_rows(const MixArgs& a, unsigned char* smem, bf16* a_lds, int a_ld, 
         const bf16x8 vq = t < a.T ? v[q] : z8;
         *(bf16x8*)(nrm + i * C + c * 8) = vq;   // history: normalised; else raw, normalised below
         if (i >= a.ctx) *(bf16x8*)(ybuf + (i - a.ctx) * C + c * 8) = vq;
-        float ss = 0.f;
-        if (t >= 0) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ss += bf(vq[j]) * bf(vq[j]);
-        }
-        ssp[e] = ss;
+        ssp[e] = t >= 0 ? cb_ss8(vq) : 0.f;
       }
     }
   }
@@ -111,7 +101,7 @@ DEV void mix_rows(const MixArgs& a, unsigned char* smem, bf16* a_lds, int a_ld, 
     const float r = inv[i];
     bf16x8 o8;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o8[j] = tobf(rb(rb(bf(v[j]) * r) * bf(wn[j])));
+    for (int j = 0; j < 8; ++j) o8[j] = cb_norm(v[j], r, wn[j]);
     *(bf16x8*)(nrm + i * C + c * 8) = o8;
     if (i >= a.ctx) *(bf16x8*)(buf + (long long)(a.ctx + t) * C + c * 8) = o8;
   }
@@ -121,20 +111,13 @@ DEV void mix_rows(const MixArgs& a, unsigned char* smem, bf16* a_lds, int a_ld, 
     const int t = t0 + i2;
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const bf16x8 v = *(const bf16x8*)(nrm + (i2 + k) * C + c2 * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f = j * 7 + k;                 // tap k of channel 8 c2 + j
-        acc[j] += bf(wk[f >> 3][f & 7]) * bf(v[j]);
-      }
-    }
+    for (int k = 0; k < 7; ++k) cb_conv8(acc, wk, *(const bf16x8*)(nrm + (i2 + k) * C + c2 * 8), k);
     const bf16x8 xv = *(const bf16x8*)(ybuf + i2 * C + c2 * 8);   // raw x row (phase 1)
     bf16x8 y8;
     float ss = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      y8[j] = tobf(bf(xv[j]) + rb(rb(acc[j] + bf(bb[j])) * bf(gv[j])));
+      y8[j] = cb_y(xv[j], acc[j], bb[j], gv[j]);
       ss += bf(y8[j]) * bf(y8[j]);
     }
     if (!TO_LDS) *(bf16x8*)(a.y + ((long long)smp * a.T + t) * C + c2 * 8) = y8;
@@ -156,7 +139,7 @@ DEV void mix_rows(const MixArgs& a, unsigned char* smem, bf16* a_lds, int a_ld, 
     const float r = inv[i2];
     bf16x8 o8;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o8[j] = tobf(rb(rb(bf(y8[j]) * r) * bf(wf[j])));
+    for (int j = 0; j < 8; ++j) o8[j] = cb_norm(y8[j], r, wf[j]);
     if (TO_LDS) *(bf16x8*)(a_lds + i2 * a_ld + c2 * 8) = o8;
     else *(bf16x8*)(a.a + ((long long)smp * a.T + t) * C + c2 * 8) = o8;
   }
@@ -247,7 +230,7 @@ __global__ void __launch_bounds__(256) k_block(BlockArgs b) {
         for (int c = 0; c < NK1; ++c) acc = mfma16(wf[j][c], *(const bf16x8*)(xrow + c * 32), acc);
         bf16x4 o;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = tobf(gelu_f(rb(acc[i] + bf(bv[i]))));
+        for (int i = 0; i < 4; ++i) o[i] = cb_gelu<false>(acc[i], bv[i]);
         *(bf16x4*)(hlds + (mt * 16 + r) * h_ld + n) = o;
         if (b.dbg_h && t0 + mt * 16 + r < a.T)
           *(bf16x4*)(b.dbg_h + ((long long)smp * a.T + t0 + mt * 16 + r) * H4 + n) = o;
@@ -266,29 +249,17 @@ __global__ void __launch_bounds__(256) k_block(BlockArgs b) {
     const int m = mt * 16 + r, t = t0 + m;
     if (t >= a.T) continue;
     const int n = nt * 16 + 4 * g;
-    const bf16x4 bv = bv2[j];
-    const bf16x4 gm = gm2[j];
     const bf16x4 yv = *(const bf16x4*)(ybuf + m * C + n);
-    bf16x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float v = rb(bf(gm[i]) * rb(acc[i] + bf(bv[i])));
-      o[i] = tobf(bf(yv[i]) + v);
-    }
-    *(bf16x4*)((bf16*)b.out.base + obase + (long long)t * b.out.sT + n) = o;
+    *(bf16x4*)((bf16*)b.out.base + obase + (long long)t * b.out.sT + n) = cb_ffn_res4(yv, acc, bv2[j], gm2[j]);
   }
 }
 
 // ================================================================ host launchers
-static size_t mix_lds_host(int R, int ctx, int C) {
-  return (size_t)(2 * R + ctx) * C * sizeof(bf16) + (size_t)(R + ctx) * (C / 8 + 1) * sizeof(float);
-}
-
 int launch_mix(MixArgs a, hipStream_t st) {
   if (a.n <= 0 || a.T <= 0) return 0;
   if (a.C % 8 || a.C > 2048 || 256 % (a.C / 8) || a.ctx != 6) return 1;   // mix_rows: 256 % n8 == 0
   if (a.R * (a.C / 8) != 256 && !(a.R == a.T && a.R * (a.C / 8) < 256)) return 1;   // one conv item per thread
-  const size_t lds = mix_lds_host(a.R, a.ctx, a.C);
+  const size_t lds = mix_lds_bytes(a.R, a.ctx, a.C);
   if (lds > 65536) return 1;
   hipLaunchKernelGGL(k_mix, dim3((a.T + a.R - 1) / a.R, a.n), dim3(256), lds, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
@@ -296,7 +267,7 @@ int launch_mix(MixArgs a, hipStream_t st) {
 
 size_t block_lds(int R, int C) {
   if (C < 32 || C > 128 || C % 32 || R % 16 || R * (C / 8) != 256) return 0;
-  const size_t base = (mix_lds_host(R, 6, C) + 15) & ~(size_t)15;
+  const size_t base = (mix_lds_bytes(R, 6, C) + 15) & ~(size_t)15;
   return base + (size_t)R * (C + 8) * sizeof(bf16) + (size_t)R * (4 * C + 8) * sizeof(bf16);
 }
 

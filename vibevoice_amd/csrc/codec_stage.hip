@@ -11,7 +11,8 @@
 //
 // Decomposition per workgroup w (C = 2,048, F = 8,192, G = 256):
 //   * front half: the control wave recomputes norm / conv / residual / FFN norm
-//     for the whole row (k_mix's and XF_MIX's arithmetic and summation order),
+//     for the whole row (codec_dev.h's arithmetic; a row's chunk sums per lane
+//     in ascending order, then the wave sum),
 //     the conv's six history taps ahead of time (during the previous block's
 //     first wait);
 //     workgroup 0 appends the new conv-input row to the block's buffer;
@@ -32,13 +33,14 @@
 // queues carry nothing but weights; the control wave does every other global
 // access.  Hand-offs: write-through stores + the grid wait of persist_dev.h.
 //
-// Arithmetic: the front half is XF_MIX's term for term (bit-identical); fc1 /
+// Arithmetic: the front half is codec_dev.h's (bit-identical to XF_MIX); fc1 /
 // fc2 are fp32 sums of exact bf16 products (v_dot2c) in a fixed order --
 // a different order than the MFMA GEMVs', so not bit-identical to the
 // launch-per-GEMV path (tests: within bf16 of it and of the oracle, bitwise
-// run to run).  Epilogues are epi_row8's EPI_GELU / EPI_RES.
+// run to run).  Epilogues are codec_dev.h's (= epi_row8's EPI_GELU / EPI_RES).
 #include <type_traits>
 
+#include "codec_dev.h"
 #include "persist_dev.h"
 
 namespace cs {
@@ -148,8 +150,8 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
   };
 
   // ---- the conv's history taps of block jb for chunks c = lane + 64 q, q in
-  // {q0, q0 + 1} (control wave): XF_MIX's tap order, taps 0..5 summed; the
-  // sum and tap 6 parked in LDS for the front half
+  // {q0, q0 + 1} (control wave): taps 0..5 summed in order; the sum and tap 6
+  // parked in LDS for the front half
   auto hist = [&](int jb, int q0) {
     const int lane = hl_vopaque((int)threadIdx.x & 63);
     const bf16* mb = hl_opaque(a.b[jb].mix) + slot * a.b[jb].mix_sB;
@@ -168,18 +170,8 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
       const int c = lane + 64 * (q0 + qq);
       float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int k = 0; k < CTX; ++k)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int f = j * 7 + k;
-          acc[j] += bf(wk[qq][f >> 3][f & 7]) * bf(hv[qq][k][j]);
-        }
-      bf16x8 t6;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f = j * 7 + 6;
-        t6[j] = wk[qq][f >> 3][f & 7];
-      }
+      for (int k = 0; k < CTX; ++k) cb_conv8(acc, wk[qq], hv[qq][k], k);
+      const bf16x8 t6 = cb_taps8(wk[qq], 6);
       *(f32x4*)(pa_s + c * 8) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
       *(f32x4*)(pa_s + c * 8 + 4) = (f32x4){acc[4], acc[5], acc[6], acc[7]};
       *(bf16x8*)(w6_s + c * 8) = t6;
@@ -210,12 +202,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
     const Block1D& B = a.b[j];
     float ss = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {   // per-chunk sums, then chunks in ascending order (XF_MIX's)
-      float s8 = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s8 += bf(xv[q][e]) * bf(xv[q][e]);
-      ss += s8;
-    }
+    for (int q = 0; q < 4; ++q) ss += cb_ss8(xv[q]);   // per-chunk sums, chunks in ascending order
     const float inv = rsqrtf(wave_sum(ss) / (float)C + a.eps);
     bf16x8 yv[4];
     float ss2 = 0.f;
@@ -225,7 +212,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
       const int c = lane + 64 * q;
       bf16x8 nr;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) nr[e] = tobf(rb(rb(bf(xv[q][e]) * inv) * bf(nw[q][e])));
+      for (int e = 0; e < 8; ++e) nr[e] = cb_norm(xv[q][e], inv, nw[q][e]);
       if (w == 0) *(bf16x8*)(nb + c * 8) = nr;   // read by the next frame's launch
       const f32x4 p0 = *(const f32x4*)(pa_s + c * 8), p1 = *(const f32x4*)(pa_s + c * 8 + 4);
       const bf16x8 t6 = *(const bf16x8*)(w6_s + c * 8);
@@ -233,8 +220,8 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
       float s8 = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        acc[e] += bf(t6[e]) * bf(nr[e]);
-        yv[q][e] = tobf(bf(xv[q][e]) + rb(rb(acc[e] + bf(db[q][e])) * bf(gm[q][e])));
+        acc[e] += bf(t6[e]) * bf(nr[e]);   // tap 6: the new row
+        yv[q][e] = cb_y(xv[q][e], acc[e], db[q][e], gm[q][e]);
         s8 += bf(yv[q][e]) * bf(yv[q][e]);
       }
       ss2 += s8;
@@ -246,7 +233,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
       const int c = lane + 64 * q;
       bf16x8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = tobf(rb(rb(bf(yv[q][e]) * inv2) * bf(fw[q][e])));
+      for (int e = 0; e < 8; ++e) o[e] = cb_norm(yv[q][e], inv2, fw[q][e]);
       *(bf16x8*)(a_s + c * 8) = o;
     }
   };
@@ -287,7 +274,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
           float sacc = 0.f;
 #pragma unroll
           for (int v = 0; v < NTC / 64; ++v) sacc += red[v * ROWS1 + u];
-          o[e] = tobf(gelu_f(rb(sacc + bf(b1[e]))));
+          o[e] = cb_gelu<false>(sacc, b1[e]);
         }
         MemWT::st8(hl_opaque(a.h) + ROWS1 * w + 4 * lane, o);
       }
@@ -314,8 +301,7 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
         float sacc = 0.f;
 #pragma unroll
         for (int v = 0; v < NTC / 64; ++v) sacc += red[v * ROWS2 + lane];
-        const float yv = rb(bf(a.b[j].ffn_gamma[col]) * rb(sacc + bf(a.b[j].fc2_b[col])));
-        const bf16 o = tobf(bf(y_s[lane]) + yv);
+        const bf16 o = cb_ffn_res(y_s[lane], sacc, a.b[j].fc2_b[col], a.b[j].ffn_gamma[col]);
         if (last) rm_bfw(a.out, 0)[col] = o;   // the launch's end publishes it
         else MemWT::st2(a.xe + col, o);
       }
@@ -460,8 +446,8 @@ __global__ void __launch_bounds__(cs::NT) k_codec_stage(CodecStageArgs a) {
 // encoder's sixth, T = 2), M = T rows of one sample.  Per workgroup and block:
 // fc1 one MFMA tile (hidden units [16w, 16w + 16), 32 KB, LDS DMA), fc2 a
 // quarter tile (output columns [4w, 4w + 4), 32 KB, registers: 4 chunks per
-// compute thread); 64 KB per CU per block.  The front half (XF_MIX's, over T
-// rows: the conv runs across the new rows and the 6 history rows) is staged in
+// compute thread); 64 KB per CU per block.  The front half (codec_dev.h's, over
+// T rows: the conv runs across the new rows and the 6 history rows) is staged in
 // LDS and computed by all nine waves (the compute waves touch no global memory
 // but their weights, so their vmcnt queue stays clean); the control wave DMAs
 // the rows in, prefetches the next block's history rows and vectors during the
@@ -560,28 +546,14 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
 #pragma unroll
       for (int k = 0; k < K7; ++k) wk[k] = hl_ld(dw + (long long)c * 56 + k * 8);
 #pragma unroll
-      for (int k = 0; k < K7; ++k) {
-        bf16x8 o;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int f = q * 7 + k;
-          o[q] = wk[f >> 3][f & 7];
-        }
-        *(bf16x8*)(vec_s + 4 * C + k * C + c * 8) = o;
-      }
+      for (int k = 0; k < K7; ++k) *(bf16x8*)(vec_s + 4 * C + k * C + c * 8) = cb_taps8(wk, k);
     }
   };
-  // every thread: per-chunk sums of squares of rows src (XF_MIX's per-chunk order) -> ssp
+  // every thread: per-chunk sums of squares of rows src -> ssp
   auto chunk_ss = [&](const bf16* src) {
-    for (int e = hl_vopaque((int)threadIdx.x); e < M * NCH; e += NT) {
-      const bf16x8 v = *(const bf16x8*)(src + e * 8);
-      float s8 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s8 += bf(v[k]) * bf(v[k]);
-      ssp[e] = s8;
-    }
+    for (int e = hl_vopaque((int)threadIdx.x); e < M * NCH; e += NT) ssp[e] = cb_ss8(*(const bf16x8*)(src + e * 8));
   };
-  // one wave per row: chunks lane, lane + 64 in order, wave_sum (XF_MIX's row order)
+  // one wave per row: chunks lane, lane + 64 in order, wave_sum (the XF_MIX prologue's row order)
   auto row_inv = [&](float* dst) {
     const int ln = hl_vopaque(lane);
     for (int m = wave; m < M; m += NT / 64) {
@@ -636,7 +608,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
       const float rr = inv_s[m];
       bf16x8 o;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = tobf(rb(rb(bf(v[k]) * rr) * bf(nw[k])));
+      for (int k = 0; k < 8; ++k) o[k] = cb_norm(v[k], rr, nw[k]);
       *(bf16x8*)(nrm_s + (CTX + m) * C + c * 8) = o;
     }
     __syncthreads();
@@ -688,7 +660,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
         float s8 = 0.f;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          y8[q] = tobf(bf(xv[q]) + rb(rb(acc[i][q] + bf(bb[q])) * bf(gv[q])));
+          y8[q] = cb_y(xv[q], acc[i][q], bb[q], gv[q]);
           s8 += bf(y8[q]) * bf(y8[q]);
         }
         *(bf16x8*)(x_s + ei * 8) = y8;
@@ -706,7 +678,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
       const float rr = inv2_s[m];
       bf16x8 o;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = tobf(rb(rb(bf(y8[k]) * rr) * bf(fw[k])));
+      for (int k = 0; k < 8; ++k) o[k] = cb_norm(y8[k], rr, fw[k]);
       *(bf16x8*)(a_s + e * 8) = o;
     }
     if (threadIdx.x < M * ROWS2) {   // y of this workgroup's 4 columns, for the fc2 epilogue
@@ -747,7 +719,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
         float sacc = 0.f;
 #pragma unroll
         for (int v = 0; v < NTC / 64; ++v) sacc += red[(v * M + m) * ROWS1 + u0 + e];
-        o[e] = tobf(gelu_f(rb(sacc + bf(b1[e]))));
+        o[e] = cb_gelu<false>(sacc, b1[e]);
       }
       MemWT::st8(hl_opaque(a.h) + (long long)m * F + ROWS1 * w + u0, o);
     }
@@ -787,8 +759,7 @@ __global__ void __launch_bounds__(cs2::NT) k_codec_stage_s(CodecStageArgs a) {
       float sacc = 0.f;
 #pragma unroll
       for (int v = 0; v < NTC / 64; ++v) sacc += red[(v * M + m) * ROWS2 + r];
-      const float yv = rb(bf(a.b[j].ffn_gamma[col]) * rb(sacc + bf(a.b[j].fc2_b[col])));
-      const bf16 o = tobf(bf(y4_s[ln]) + yv);
+      const bf16 o = cb_ffn_res(y4_s[ln], sacc, a.b[j].fc2_b[col], a.b[j].ffn_gamma[col]);
       if (last) rm_bfw(a.out, m)[col] = o;
       else MemWT::st2(hl_opaque(a.xe) + (long long)m * C + col, o);
     }

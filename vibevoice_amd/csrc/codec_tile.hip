@@ -19,10 +19,9 @@
 // RMSNorm (one 16-byte chunk per thread, a row's chunks in one lane group so the
 // row sums are DPP reductions in registers) -> fc1 (MFMA 16x16x32, weights in
 // registers, hidden rows + GELU into LDS) -> fc2 (MFMA) -> ffn_gamma residual.
-// The arithmetic is k_block's / k_mix's term for term (codec_block.hip) except
-// the GELU: erf by a 5-term rational approximation (gelu_fast, |error| <= 1.5e-7
-// before the bf16 rounding of the output) instead of ocml's erff, whose two
-// branch paths made fc1 + GELU ~8 us of a C = 128 block (tools/codec_tile_stamps.py).
+// The arithmetic is codec_dev.h's, with the GELU by gelu_fast: ocml's erff, with
+// its two branch paths, made fc1 + GELU ~8 us of a C = 128 block
+// (tools/codec_tile_stamps.py).
 // The transition GEMM sums its 32-wide K chunks in order in one fp32 accumulator
 // (EPI_STORE's rounding); the head conv is k_conv_cout1's order.
 //
@@ -32,17 +31,17 @@
 // fc1 products, its fc2 fragments after block j's fc2 products, so every weight
 // fragment has a whole phase to arrive.  All loads are branch-free (clamped
 // addresses) so hipcc's vmcnt accounting stays exact in the unrolled code.
-#include "kernels.h"
+#include "codec_dev.h"
 
 namespace ct {
-constexpr int NTH = 512, NW = 8;   // 8 waves
+using ctm::NTH;
+using ctm::NW;
 template <int C, int R_>
-struct Geo {
+struct Geo : ctm::Geo<C> {
+  using ctm::Geo<C>::F;
+  using ctm::Geo<C>::XLD;
   static constexpr int R = R_;                   // output rows per workgroup (16, or 2048 / C for many samples)
-  static constexpr int N8 = C / 8;               // 16-byte chunks per row
-  static constexpr int RPP = NTH / N8;           // rows per elementwise pass
-  static constexpr int F = 4 * C;
-  static constexpr int XLD = C + 8, HLD = F + 8; // LDS row strides (+16 B against bank conflicts)
+  static constexpr int HLD = F + 8;              // hidden rows' LDS stride
   static constexpr int NLP = (R + 24 + 15) / 16 * 16;   // local rows (halo 18 + head 6), padded to tiles
   static constexpr int NT1 = F / 16, NK1 = C / 32, NT2 = C / 16, NK2 = F / 32;
   // LDS carve-up (bytes)
@@ -54,7 +53,6 @@ struct Geo {
   static constexpr int H = A + A_B, H_B = (NLP + 16) * HLD * 2;       // hidden rows (transition input first)
   static constexpr int TOTAL = H + H_B;
   static_assert(TOTAL <= 160 * 1024, "one workgroup per CU at most");
-  static_assert(NTH % N8 == 0 && 64 % N8 == 0, "a row's chunks in one lane group");
 };
 // a GEMM of NT 16-row weight tiles over 8 waves: NTW tiles per wave, row tiles strided by RS
 template <int NT>
@@ -131,8 +129,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
   }
 
   // ---------------------------------------------------------------- per-block operands
-  struct Aux {   // one set in registers: block j+1's overwrites block j's once its mixer and fc1 are done
-    bf16x8 wn, bb, gv, wf, wk[7], hv;
+  struct Aux : TileMix<C> {   // + fc1's biases of this wave's tiles
     bf16x4 b1[ct::Split<G::NT1>::NTW];
   };
   using S1 = ct::Split<G::NT1>;
@@ -142,14 +139,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
   const int rs2 = G::NT2 >= NW ? 0 : wave / G::NT2;
   auto load_aux = [&](int j, Aux& x) {
     const Block1D& b = a.b[j];
-    x.wn = *(const bf16x8*)(b.norm + c2 * 8);
-    x.bb = *(const bf16x8*)(b.dw_b + c2 * 8);
-    x.gv = *(const bf16x8*)(b.gamma + c2 * 8);
-    x.wf = *(const bf16x8*)(b.ffn_norm + c2 * 8);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) x.wk[k] = *(const bf16x8*)(b.dw_w + (size_t)c2 * 56 + k * 8);
-    const int h = min(tid / G::N8, 5);   // history row h (threads >= 6 * N8 load a copy of row 5)
-    x.hv = *(const bf16x8*)(b.mix + slot * b.mix_sB + (long long)h * C + c2 * 8);
+    CB_TILE_MIX_LOAD(G, C, x, b, slot, tid, c2);
 #pragma unroll
     for (int i = 0; i < S1::NTW; ++i) x.b1[i] = *(const bf16x4*)(b.fc1_b + (nt1 + i) * 16 + 4 * g4);
   };
@@ -259,62 +249,12 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
   for (int j = 0; j < 3; ++j) {
     const Block1D& bj = a.b[j];
     const int lo = max(0, L0 + 6 * (j + 1));   // first output row of block j
-    const int cs = lo - 6;                       // first conv input row
-    // ---- M1: conv input rows = norm(x) (history rows t < 0 from the buffer)
-    if (tid < 6 * G::N8) {
-      const int t = tid / G::N8 - 6;
-      if (t >= cs) *(bf16x8*)(ns + (t - L0 + 6) * G::XLD + c2 * 8) = ax.hv;
-    }
-    const int r0 = max(cs, 0);
-    for (int p = r0; p < B; p += G::RPP) {
-      const int t = p + rp, tc = min(t, B - 1);
-      const bf16x8 v = *(const bf16x8*)(xs + (tc - L0) * G::XLD + c2 * 8);
-      float ss = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ss += bf(v[q]) * bf(v[q]);
-      ss = group_sum<G::N8>(ss);
-      const float inv = rsqrtf(ss / (float)C + a.eps);
-      bf16x8 o8;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) o8[q] = tobf(rb(rb(bf(v[q]) * inv) * bf(ax.wn[q])));
-      if (t < B) {
-        *(bf16x8*)(ns + (t - L0 + 6) * G::XLD + c2 * 8) = o8;
-        if (t >= T - 6) *(bf16x8*)(bj.mix + slot * bj.mix_sB + (long long)(6 + t) * C + c2 * 8) = o8;
-      }
-    }
+    // ---- M1: conv input rows = norm(x); every tile workgroup is its history rows' only writer
+    CB_TILE_MIX_NORM(G, C, ax, bj, slot, a.eps, xs, ns, L0, lo, B, T, true, tid, c2, rp);
     __syncthreads();
     stamp(3 + 4 * j);
     // ---- M2: depthwise conv + gamma residual -> y; FFN norm -> fc1's input rows
-    for (int p = lo; p < B; p += G::RPP) {
-      const int t = p + rp, tc = min(t, B - 1);
-      float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const bf16x8 v = *(const bf16x8*)(ns + (tc - L0 + k) * G::XLD + c2 * 8);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int f = q * 7 + k;
-          acc[q] += bf(ax.wk[f >> 3][f & 7]) * bf(v[q]);
-        }
-      }
-      const bf16x8 xv = *(const bf16x8*)(xs + (tc - L0) * G::XLD + c2 * 8);
-      bf16x8 y8;
-      float ss = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        y8[q] = tobf(bf(xv[q]) + rb(rb(acc[q] + bf(ax.bb[q])) * bf(ax.gv[q])));
-        ss += bf(y8[q]) * bf(y8[q]);
-      }
-      ss = group_sum<G::N8>(ss);
-      const float inv = rsqrtf(ss / (float)C + a.eps);
-      bf16x8 o8;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) o8[q] = tobf(rb(rb(bf(y8[q]) * inv) * bf(ax.wf[q])));
-      if (t < B) {
-        *(bf16x8*)(ys + (t - L0) * G::XLD + c2 * 8) = y8;
-        *(bf16x8*)(as + (t - L0) * G::XLD + c2 * 8) = o8;
-      }
-    }
+    CB_TILE_MIX_CONV(G, C, ax, a.eps, xs, ns, ys, as, L0, lo, B, c2, rp);
     __syncthreads();
     stamp(4 + 4 * j);
     // row tiles start at the block's first output row (local row lo - L0), not on a
@@ -330,9 +270,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
           f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int c = 0; c < G::NK1; ++c) acc = mfma16(w1[i * G::NK1 + c], *(const bf16x8*)(xrow + c * 32), acc);
-          bf16x4 o;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = tobf(gelu_fast(rb(acc[q] + bf(ax.b1[i][q]))));
+          const bf16x4 o = cb_gelu4<true>(acc, ax.b1[i]);
           *(bf16x4*)(hs + (rb0 + mt * 16 + r16) * G::HLD + (nt1 + i) * 16 + 4 * g4) = o;
         }
       }
@@ -352,9 +290,7 @@ __global__ void __launch_bounds__(ct::NTH, 1) k_codec_tile(CodecTileArgs a) {
         const int n = nt2 * 16 + 4 * g4;
         if (t >= lo && t < B) {
           const bf16x4 yv = *(const bf16x4*)(ys + (t - L0) * G::XLD + n);
-          bf16x4 o;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = tobf(bf(yv[q]) + rb(bf(g2c[q]) * rb(acc[q] + bf(b2c[q]))));
+          const bf16x4 o = cb_ffn_res4(yv, acc, b2c, g2c);
           *(bf16x4*)(xs + (t - L0) * G::XLD + n) = o;
           if (j == 2 && POST == CT_POST_NONE && t >= t0) *(bf16x4*)(rm_bfw(a.out, smp * T + t) + n) = o;
         }

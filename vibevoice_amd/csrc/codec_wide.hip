@@ -8,7 +8,7 @@
 // Here a CLUSTER of S = C / 32 workgroups shares each 16-row time tile:
 //   * every member recomputes the tile's causal halo and mixer (norm ->
 //     depthwise conv -> gamma residual -> FFN norm) for all C channels
-//     (codec_tile.hip's arithmetic: rows t < 0 from the conv histories);
+//     (codec_dev.h's arithmetic: rows t < 0 from the conv histories);
 //   * member s owns hidden units [128 s, 128 s + 128): fc1 over them (MFMA, its
 //     8 weight tiles in registers, one per wave) -> GELU -> hidden slice in LDS
 //     -> its K-slice of fc2 (MFMA) = an fp32 partial of the block output;
@@ -25,23 +25,29 @@
 // it only under the grid-waiting kernels' rule (persist_on) and otherwise takes
 // the launch-per-op path.
 #include <atomic>
+#include <type_traits>
 
+#include "codec_dev.h"
 #include "persist_dev.h"
 
 namespace cw {
-constexpr int NTH = 512, NW = 8;
+using ctm::NTH;
+using ctm::NW;
 template <int C>
-struct Geo {
+struct Geo : ctm::Geo<C> {
+  using ctm::Geo<C>::F;
+  using ctm::Geo<C>::XLD;
   static constexpr int S = C / 32;               // cluster members (8 / 16)
   static constexpr int R = 16;                   // output rows per tile
-  static constexpr int N8 = C / 8, RPP = NTH / N8;
-  static constexpr int F = 4 * C, HSL = 128;     // hidden units per member
+  static constexpr int HSL = 128;                // hidden units per member
   static constexpr int NL = R + 18;              // local rows (halo of three k = 7 convs)
-  static constexpr int XLD = C + 8, HLD = HSL + 8;
+  static constexpr int HLD = HSL + 8;
   static constexpr int NK1 = C / 32;             // fc1 K chunks (one 16-unit tile per wave)
   static constexpr int NTW2 = C / 16 / NW;       // fc2 output tiles per wave (2 / 4)
   static constexpr int NK2F = F / 32;            // fc2 K chunks of the whole hidden width
-  static constexpr int PR = 40;                  // rows of a partial slab
+  static constexpr int PR = 40;                  // rows of a partial slab (>= NL)
+  // workspace per (sample, tile) cluster: S fp32 partial slabs, one bf16 block output
+  static constexpr size_t SLAB = (size_t)S * PR * C, XBUF = (size_t)PR * C;
   // LDS (bytes): x rows (y in place after the conv), conv input rows, fc1 input
   // rows, hidden slice (+16 rows: row tiles start at the block's first row)
   static constexpr int X = 0, X_B = NL * XLD * 2;
@@ -90,8 +96,8 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
   const bool last_tile = B == T;
   const int cluster = smp * ntiles + tile;
   unsigned* cnt = a.sync + (long long)cluster * pk::LINE;
-  float* slab = a.slab + (long long)cluster * G::S * G::PR * C;
-  bf16* xg = a.xbuf + (long long)cluster * G::PR * C;
+  float* slab = a.slab + (long long)cluster * G::SLAB;
+  bf16* xg = a.xbuf + (long long)cluster * G::XBUF;
   unsigned base = 0, nwait = 0;
   if (tid == 0)   // fewer than S arrivals can precede this read (this member's own is missing)
     base = __hip_atomic_load((hl_gu32*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / G::S * G::S;
@@ -126,22 +132,14 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
     vin[q] = *(const bf16x8*)(a.x + ((long long)smp * T + S_lo + i) * C + c * 8);
   }
   // ---------------------------------------------------------------- operands of a block
-  struct Aux {
-    bf16x8 wn, bb, gv, wf, wk[7], hv;
+  struct Aux : TileMix<C> {   // + this wave's fc1 biases, this thread's fc2 bias / ffn_gamma columns
     bf16x4 b1, b2, g2;
   };
   const int nu = s * G::HSL + wave * 16;        // this wave's fc1 tile: hidden units nu .. nu + 15
   const int rcol = s * 32 + 4 * (tid & 7);      // reduce-scatter: this thread's 4 output columns
   auto load_aux = [&](int j, Aux& x) {
     const Block1D& b = a.b[j];
-    x.wn = *(const bf16x8*)(b.norm + c2 * 8);
-    x.bb = *(const bf16x8*)(b.dw_b + c2 * 8);
-    x.gv = *(const bf16x8*)(b.gamma + c2 * 8);
-    x.wf = *(const bf16x8*)(b.ffn_norm + c2 * 8);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) x.wk[k] = *(const bf16x8*)(b.dw_w + (size_t)c2 * 56 + k * 8);
-    const int h = min(tid / G::N8, 5);
-    x.hv = *(const bf16x8*)(b.mix + slot * b.mix_sB + (long long)h * C + c2 * 8);
+    CB_TILE_MIX_LOAD(G, C, x, b, slot, tid, c2);
     x.b1 = *(const bf16x4*)(b.fc1_b + nu + 4 * g4);
     x.b2 = *(const bf16x4*)(b.fc2_b + rcol);
     x.g2 = *(const bf16x4*)(b.ffn_gamma + rcol);
@@ -181,62 +179,13 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
   for (int j = 0; j < 3; ++j) {
     const Block1D& bj = a.b[j];
     const int lo = max(0, L0 + 6 * (j + 1));
-    const int cs = lo - 6;
-    // ---- M1: conv input rows = norm(x) (history rows t < 0 from the buffer)
-    if (tid < 6 * G::N8) {
-      const int t = tid / G::N8 - 6;
-      if (t >= cs) *(bf16x8*)(ns + (t - L0 + 6) * G::XLD + c2 * 8) = ax.hv;
-    }
-    for (int p = max(cs, 0); p < B; p += G::RPP) {
-      const int t = p + rp, tc = min(t, B - 1);
-      const bf16x8 v = *(const bf16x8*)(xs + (tc - L0) * G::XLD + c2 * 8);
-      float ss = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ss += bf(v[q]) * bf(v[q]);
-      ss = group_sum<G::N8>(ss);
-      const float inv = rsqrtf(ss / (float)C + a.eps);
-      bf16x8 o8;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) o8[q] = tobf(rb(rb(bf(v[q]) * inv) * bf(ax.wn[q])));
-      if (t < B) {
-        *(bf16x8*)(ns + (t - L0 + 6) * G::XLD + c2 * 8) = o8;
-        if (s == 0 && t >= T - 6) *(bf16x8*)(bj.mix + slot * bj.mix_sB + (long long)(6 + t) * C + c2 * 8) = o8;
-      }
-    }
+    // ---- M1: conv input rows = norm(x); member 0 appends the tile's history rows
+    CB_TILE_MIX_NORM(G, C, ax, bj, slot, a.eps, xs, ns, L0, lo, B, T, s == 0, tid, c2, rp);
     constexpr bool W2_LATE = G::NK1 > 8;   // C = 512: fc2's fragments only after fc1's are consumed (registers)
     if (!W2_LATE) load_w2(j);
     __syncthreads();
     // ---- M2: depthwise conv + gamma residual -> y (over x, in place); FFN norm -> fc1's input rows
-    for (int p = lo; p < B; p += G::RPP) {
-      const int t = p + rp, tc = min(t, B - 1);
-      float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const bf16x8 v = *(const bf16x8*)(ns + (tc - L0 + k) * G::XLD + c2 * 8);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int f = q * 7 + k;
-          acc[q] += bf(ax.wk[f >> 3][f & 7]) * bf(v[q]);
-        }
-      }
-      const bf16x8 xv = *(const bf16x8*)(xs + (tc - L0) * G::XLD + c2 * 8);
-      bf16x8 y8;
-      float ss = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        y8[q] = tobf(bf(xv[q]) + rb(rb(acc[q] + bf(ax.bb[q])) * bf(ax.gv[q])));
-        ss += bf(y8[q]) * bf(y8[q]);
-      }
-      ss = group_sum<G::N8>(ss);
-      const float inv = rsqrtf(ss / (float)C + a.eps);
-      bf16x8 o8;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) o8[q] = tobf(rb(rb(bf(y8[q]) * inv) * bf(ax.wf[q])));
-      if (t < B) {   // (item (t, c2) is read and written by this thread alone: y over x in place)
-        *(bf16x8*)(xs + (t - L0) * G::XLD + c2 * 8) = y8;
-        *(bf16x8*)(as + (t - L0) * G::XLD + c2 * 8) = o8;
-      }
-    }
+    CB_TILE_MIX_CONV(G, C, ax, a.eps, xs, ns, xs, as, L0, lo, B, c2, rp);
     __syncthreads();
     stamp(2 + 4 * j);
     const int rb0 = lo - L0, nmt = (B - lo + 15) >> 4;
@@ -248,9 +197,7 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < G::NK1; ++c) acc = mfma16(w1[c], *(const bf16x8*)(xrow + c * 32), acc);
-        bf16x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = tobf(gelu_fast(rb(acc[q] + bf(b1[q]))));
+        const bf16x4 o = cb_gelu4<true>(acc, b1);
         *(bf16x4*)(hs + (rb0 + mt * 16 + r16) * G::HLD + wave * 16 + 4 * g4) = o;
       }
     }
@@ -292,9 +239,7 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
             for (int m = 0; m < 8; ++m) acc = m0 + m == 0 ? v[m] : acc + v[m];
           }
           const bf16x4 yv = *(const bf16x4*)(xs + (t - L0) * G::XLD + rcol);
-          bf16x4 o;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = tobf(bf(yv[q]) + rb(bf(ax.g2[q]) * rb(acc[q] + bf(ax.b2[q]))));
+          const bf16x4 o = cb_ffn_res4(yv, acc, ax.b2, ax.g2);
           if (j < 2) MemWT::st8(xg + (long long)(t - L0) * C + rcol, o);
           else if (t >= t0) *(bf16x4*)(rm_bfw(a.out, smp * T + t) + rcol) = o;
         }
@@ -330,9 +275,20 @@ __global__ void __launch_bounds__(cw::NTH, 1) k_codec_wide(CodecWideArgs a) {
 }
 
 // ================================================================ host
+// f(C as a constant) for the C the cluster kernel is built for; `none` otherwise
+template <typename F, typename R>
+static R cw_for(int C, R none, F&& f) {
+  return C == 256 ? f(std::integral_constant<int, 256>()) : C == 512 ? f(std::integral_constant<int, 512>()) : none;
+}
+template <int C>
+static size_t cw_clusters(int T, int n) { return (size_t)n * ((T + cw::Geo<C>::R - 1) / cw::Geo<C>::R); }
+
 template <int C>
 static int cw_launch(const CodecWideArgs& a, hipStream_t st) {
   using G = cw::Geo<C>;
+  static const bool attr = hipFuncSetAttribute((const void*)k_codec_wide<C>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               G::TOTAL) == hipSuccess;
+  if (!attr) return 2;
   const int tiles = (a.T + G::R - 1) / G::R;
   hipLaunchKernelGGL(k_codec_wide<C>, dim3(tiles * G::S, a.n), dim3(cw::NTH), G::TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? 0 : 2;
@@ -374,23 +330,16 @@ bool codec_wide_fits(int C, int T, int n, int depth, int ctx) {
 }
 
 // workspace: sync lines per cluster, partial slabs, block outputs
+// (0 for a C the kernel is not built for: the engine sizes these only for a stage routed here)
 size_t codec_wide_slab_floats(int C, int T, int n) {
-  const int tiles = (T + 15) / 16;
-  return (size_t)n * tiles * (C / 32) * 40 * C;
+  return cw_for(C, (size_t)0, [&](auto c) { return cw_clusters<c()>(T, n) * cw::Geo<c()>::SLAB; });
 }
-size_t codec_wide_xbuf_elems(int C, int T, int n) { return (size_t)n * ((T + 15) / 16) * 40 * C; }
+size_t codec_wide_xbuf_elems(int C, int T, int n) {
+  return cw_for(C, (size_t)0, [&](auto c) { return cw_clusters<c()>(T, n) * cw::Geo<c()>::XBUF; });
+}
 
 int launch_codec_wide(const CodecWideArgs& a, int C, hipStream_t st) {
   if (a.n <= 0 || a.T <= 0) return 0;
   if (!codec_wide_fits(C, a.T, a.n, a.depth, 6)) return 3;
-  if (C == 256) {
-    static const bool attr = hipFuncSetAttribute((const void*)k_codec_wide<256>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, cw::Geo<256>::TOTAL) == hipSuccess;
-    if (!attr) return 2;
-    return cw_launch<256>(a, st);
-  }
-  static const bool attr = hipFuncSetAttribute((const void*)k_codec_wide<512>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, cw::Geo<512>::TOTAL) == hipSuccess;
-  if (!attr) return 2;
-  return cw_launch<512>(a, st);
+  return cw_for(C, 1, [&](auto c) { return cw_launch<c()>(a, st); });
 }

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "attn_dev.h"
+#include "codec_dev.h"
 #include "kernels.h"
 #include "gemv_dev.h"
 
@@ -370,8 +371,8 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
       *(bf16x8*)(xs + m * lds_ld + k) = o8;
     }
   } else if (XF == XF_MIX) {
-    // Codec Block1D front half for the M = ns * T rows (k_mix's math and
-    // summation order, elementwise.hip): every workgroup recomputes it (a few
+    // Codec Block1D front half for the M = ns * T rows (codec_dev.h's arithmetic,
+    // a row's chunk sums added in k_mix's order): every workgroup recomputes it (a few
     // tens of KB of L2 reads next to its weight slice); workgroup 0 also stores
     // the conv-buffer rows and y.  One dependent global round trip: operands,
     // x rows and history rows are issued together ahead of the weight stream
@@ -423,10 +424,7 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
         const int R = r0 + rt + q * rpt;
         if (R < a.M) {
           *(bf16x8*)(xs + R * lds_ld + c2 * 8) = v[q];
-          float ss = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ss += bf(v[q][j]) * bf(v[q][j]);
-          ssp[R * n8 + c2] = ss;
+          ssp[R * n8 + c2] = cb_ss8(v[q]);
         } else if (R < nrow) {
           const int hr = R - a.M, s_ = hr / CTX;
           *(bf16x8*)(nrm + ((size_t)s_ * (CTX + T) + (hr - s_ * CTX)) * C + c2 * 8) = v[q];
@@ -448,7 +446,7 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
       const float rr = inv_s[m];
       bf16x8 o8;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o8[j] = tobf(rb(rb(bf(v[j]) * rr) * bf(wn[j])));
+      for (int j = 0; j < 8; ++j) o8[j] = cb_norm(v[j], rr, wn[j]);
       *(bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + ctx + t) * C + c2 * 8) = o8;
       if (writer) {
         long long sb = sbase[0];
@@ -463,21 +461,15 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
       const int m = e / n8, s_ = m / T, t = m - s_ * T;
       float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const bf16x8 v = *(const bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + t + k) * C + c2 * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int f = j * 7 + k;
-          acc[j] += bf(wk[f >> 3][f & 7]) * bf(v[j]);
-        }
-      }
+      for (int k = 0; k < 7; ++k)
+        cb_conv8(acc, wk, *(const bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + t + k) * C + c2 * 8), k);
       bf16x8* px = (bf16x8*)(xs + m * lds_ld + c2 * 8);
       const bf16x8 xv = *px;
       bf16x8 y8;
       float ss = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        y8[j] = tobf(bf(xv[j]) + rb(rb(acc[j] + bf(bb[j])) * bf(gv[j])));
+        y8[j] = cb_y(xv[j], acc[j], bb[j], gv[j]);
         ss += bf(y8[j]) * bf(y8[j]);
       }
       if (writer) *(bf16x8*)(a.xf.y + (long long)m * C + c2 * 8) = y8;
@@ -499,7 +491,7 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
       const float rr = inv_s[m];
       bf16x8 o8;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o8[j] = tobf(rb(rb(bf(y8[j]) * rr) * bf(wf[j])));
+      for (int j = 0; j < 8; ++j) o8[j] = cb_norm(y8[j], rr, wf[j]);
       *px = o8;
     }
   } else if (fast) {
