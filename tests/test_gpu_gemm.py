@@ -107,6 +107,49 @@ def test_fused_rmsnorm_producer(M, N, K, weighted):
     assert e < 4e-3
 
 
+@pytest.mark.parametrize("M,K,waves,weighted", [(2, 1536, 0, True), (16, 1536, 8, True), (4, 3584, 0, False)])
+def test_norm_row_per_wave_equals_item_form(M, K, waves, weighted):
+    """The summation-order contract of k_gemv1's norm prologues (gemv_dev.h ss8 /
+    ss8_run): the row-per-wave forms (3 items per lane x 1 row per wave, x 2 rows
+    per wave at 16 rows on 8 waves, 7 items per lane) give the bits of the
+    item-per-thread form of the same launch (vv_gemv_tune_rw(99))."""
+    L = _lib.lib()
+    N = 256
+    g = torch.Generator(device=dev).manual_seed(M + K)
+    A = (3 * torch.randn(M, K, device=dev, generator=g)).bfloat16()
+    Wp = mfma_pack((torch.randn(N, K, device=dev, generator=g) / K ** 0.5).bfloat16())
+    nw = (1 + 0.2 * torch.randn(K, device=dev, generator=g)).bfloat16() if weighted else None
+
+    def plan():
+        pl = (ctypes.c_int * 7)()
+        _lib.check(L.vv_gemv_plan(M, N, K, 1, int(weighted), 0, pl), "gemv_plan")
+        return list(pl)
+
+    def launch():
+        Y = torch.zeros(M, N, device=dev, dtype=torch.bfloat16)
+        _lib.check(L.vv_gemm_bf16_norm(M, N, K, P(A), K, P(nw), 1e-6, P(Wp), _lib.EPI["store"], P(Y), N, None,
+                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gemm_norm")
+        torch.cuda.synchronize()
+        return Y
+
+    try:
+        # the plans of both states first: k_gemv1 (A staged in LDS) on the same waves, K splits and chunks in
+        # flight, and only the prologue form differs -- so the launches below cannot be one form twice
+        L.vv_gemv_tune(waves, 0, -1, 0, 0)
+        p_rw = plan()
+        L.vv_gemv_tune_rw(99)
+        p_item = plan()
+        assert p_rw[0] == 0 and p_rw[5] == 1 and p_item[5] == 0, (p_rw, p_item)
+        assert p_rw[:5] == p_item[:5] and (waves == 0 or p_rw[1] == waves), (p_rw, p_item)
+        Y_item = launch()
+        L.vv_gemv_tune_rw(0)
+        Y_rw = launch()
+    finally:
+        L.vv_gemv_tune_rw(0)
+        L.vv_gemv_tune(0, 0, -1, 0, 0)
+    assert Y_rw.abs().sum() > 0 and torch.equal(Y_rw, Y_item)
+
+
 @pytest.mark.parametrize("tpw", [0, 1, 2, 4, 8])
 @pytest.mark.parametrize("M,N,epi", [(16, 8208, "store"), (8, 8192, "res"), (12, 17920, "silu_mul"),
                                      (2, 2064, "store")])

@@ -21,16 +21,11 @@
 // Block1D arithmetic").  The chunk-wide helpers below are the ones that left
 // every kernel's loads, waits, barriers and registers where they were.
 #pragma once
-#include "kernels.h"
+#include "gemv_dev.h"
 
 // ---------------------------------------------------------------- element arithmetic
 // sum of squares of a chunk, ascending element order (a row's sum adds its chunks' sums)
-DEV float cb_ss8(bf16x8 v) {
-  float ss = 0.f;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) ss += bf(v[q]) * bf(v[q]);
-  return ss;
-}
+DEV float cb_ss8(bf16x8 v) { return ss8(v); }
 // ConvRMSNorm of an element, inv = rsqrt(mean square + eps): the mixer norm and the FFN norm
 DEV bf16 cb_norm(bf16 v, float inv, bf16 w) { return tobf(rb(rb(bf(v) * inv) * bf(w))); }
 // The depthwise weights are [C][7]: a chunk's 56 values in 7 registers wk, tap k

@@ -55,14 +55,7 @@ DEV void stamp(const GemmArgs& a, int which) {
 }
 
 // ------------------------------------------------------------------ GEMV
-// Index math of the prologues.  blockDim.x is a 16-bit implicit kernel
-// argument; gfx950 has no 16-bit scalar load, so a read of it that the
-// compiler cannot prove unclobbered (any global store earlier in the kernel,
-// e.g. a timing stamp) becomes a VECTOR load + s_waitcnt vmcnt(0): a whole
-// memory round trip before the first A / weight load was issued.  Kernels read
-// it once, first (a scalar load), and the K ranges use 32-bit arithmetic (the
-// 64-bit divisions were ~300 VALU instructions ahead of the first load).
-DEV int part_of(int len, int i, int n) { return (int)((unsigned)(len * i) / (unsigned)n); }
+// (the K-range index math and its "read blockDim first" rule: gemv_dev.h part_of, k_range)
 // Split-K hand-off of the 16 x (16*MREP) fp32 tile between the workgroups of one
 // tile column: every split stores its slab, takes a ticket, the last arriver
 // sums the slabs in split order (deterministic) and runs the epilogue.
@@ -128,6 +121,412 @@ DEV bool splitk_handoff(const GemmArgs& a, float* red, int TILE, unsigned* last_
 // TPW = 5: the balanced many-tile form (gemm_decide): one workgroup per CU, 4 or
 // 5 tiles each, 2 waves per tile (10 waves)
 constexpr int gemv1_max_waves(int tpw) { return tpw == 5 ? 10 : 8; }
+constexpr int GEMV1_Q = 4;   // A items per thread on the fast path
+// ---- A staging into LDS (rows [0, M) x chunks [b0, b1), row stride padded
+// 16 B), overlapped with the first weight chunks: six prologue forms, each
+// given the workgroup's geometry and `first`, the callable that issues the
+// wave's first weight batch.  vmcnt waits are in issue order, so every form
+// that waits on A-side loads (row chunk + its transform operands) issues them
+// BEFORE first(): the prologue then waits only for its own bytes and the
+// weight stream stays in flight through the norm math.
+struct Gemv1Geo {
+  int NT, NW, lane, wave;
+  int b0;            // first chunk of the workgroup's K range
+  int n8, lds_ld;    // 8-element items staged per row; LDS row stride in elements
+  bool fast;         // M * n8 <= GEMV1_Q * NT: the item form holds every item in registers (ss8's contract)
+  bf16* xs;          // the staged rows
+  float* part;       // LDS behind them: partial sums (XF_MIX: its conv rows, then the sums)
+  float* inv_s;      // [16]
+};
+// One whole row in a wave's registers (lane l: items l, l + 64, ..): its sum of
+// squares in the order the item form gives that row (ss8's contract), wave_sum,
+// inverse RMS, and for a real row (store) the norm chain into its LDS row.
+// (the uniform has_w / has_mod tests stay per element: hoisting them into
+// specialised copies raised the kernel to 180 VGPRs, 3 -> 2 waves / SIMD)
+template <int IPR, bool MOD>
+DEV void rw_row_norm(const GemmArgs& a, const Gemv1Geo& g, const bf16x8* xv, const bf16x8* wv, const bf16x8* sc,
+                     const bf16x8* sh, bool has_w, bool has_mod, bool store, bf16* xrow_l) {
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < IPR; ++i) {
+    if (g.fast) ss += ss8(xv[i]);
+    else ss = ss8_run(ss, xv[i]);
+  }
+  ss = wave_sum(ss);
+  const float inv = rsqrtf(ss / (float)a.K + a.xf.eps);
+  if (store) {
+#pragma unroll
+    for (int i = 0; i < IPR; ++i) {
+      bf16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        o[j] = norm_rt(xv[i][j], inv, has_w, wv[i][j], has_mod, sc[MOD ? i : 0][j], sh[MOD ? i : 0][j]);
+      *(bf16x8*)(xrow_l + (g.lane + 64 * i) * 8) = o;
+    }
+  }
+}
+// RW = 1, row-per-wave norm: IPR items per lane per row x RPW rows per wave; MOD:
+// adaLN operands possible (their registers reserved).  Loads (A, norm weight,
+// adaLN shift / scale; all unconditional, clamped to valid rows, so no branch
+// join waits on them), then the weight stream, then rw_row_norm per row.
+template <int IPR, int RPW, bool MOD, class F>
+DEV void gemv1_stage_rw(const GemmArgs& a, const Gemv1Geo& g, F first) {
+  constexpr int QR = IPR * RPW;
+  const int lane = g.lane, wave = g.wave;
+  bf16x8 xv[QR], wv[QR], sh[MOD ? QR : 1], sc[MOD ? QR : 1];
+  const bool has_w = a.xf.w != nullptr, has_mod = MOD && a.xf.mod != nullptr;
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int m = min(wave * RPW + r, a.M - 1);
+    const bf16* xr = rm_bf(a.a, m);
+    const bf16* wp = has_w ? a.xf.w : xr;
+    const bf16* md = has_mod ? a.xf.mod + (long long)m * a.xf.mod_ld : xr;
+    const int so = has_mod ? a.xf.shift_off : 0, co = has_mod ? a.xf.scale_off : 0;
+#pragma unroll
+    for (int i = 0; i < IPR; ++i) {
+      const int k = (lane + 64 * i) * 8;
+      xv[r * IPR + i] = *(const bf16x8*)(xr + k);
+      wv[r * IPR + i] = *(const bf16x8*)(wp + k);
+      if (has_mod) {
+        sh[MOD ? r * IPR + i : 0] = *(const bf16x8*)(md + so + k);
+        sc[MOD ? r * IPR + i : 0] = *(const bf16x8*)(md + co + k);
+      }
+    }
+  }
+  first();
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int m = wave * RPW + r;
+    rw_row_norm<IPR, MOD>(a, g, xv + r * IPR, wv + r * IPR, sc + (MOD ? r * IPR : 0), sh + (MOD ? r * IPR : 0), has_w,
+                          has_mod, m < a.M, g.xs + m * g.lds_ld);
+  }
+}
+// RW = 2, K = 3,584 rows with adaLN operands (VibeVoice-Large head): the raw A row
+// goes straight to its LDS row by 16-byte LDS DMA (lane l's item i lands at
+// (l + 64 i) * 8, the row layout), so only the norm weight and shift / scale
+// take registers; the row is read back by its own lanes after a counted vmcnt
+// (the 21 operand loads and the U weight loads issued after it stay in flight).
+// Then rw_row_norm, gemv1_stage_rw's row tail, the modulation unconditional.
+template <int U, class F>
+DEV void gemv1_stage_rw_dma(const GemmArgs& a, const Gemv1Geo& g, F first) {
+  constexpr int IPR = 7;
+  const int lane = g.lane, wave = g.wave;
+  bf16x8 wv[IPR], sh[IPR], sc[IPR];
+  const bool has_w = a.xf.w != nullptr;
+  const int m = min(wave, a.M - 1);
+  bf16* xrow_l = g.xs + m * g.lds_ld;
+  if (wave < a.M) {
+    const bf16* xr = rm_bf(a.a, m);
+    const bf16* wp = has_w ? a.xf.w : xr;
+    const bf16* md = a.xf.mod + (long long)m * a.xf.mod_ld;
+#pragma unroll
+    for (int i = 0; i < IPR; ++i)
+      __builtin_amdgcn_global_load_lds((const void*)(xr + (lane + 64 * i) * 8),
+                                       (__attribute__((address_space(3))) void*)(xrow_l + 64 * i * 8), 16, 0, 0);
+    // the counted wait below needs exactly these loads younger than the DMA,
+    // in this order: sched_barrier fences keep the scheduler from moving any
+    // of them across
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < IPR; ++i) {
+      const int k = (lane + 64 * i) * 8;
+      wv[i] = *(const bf16x8*)(wp + k);
+      sh[i] = *(const bf16x8*)(md + a.xf.shift_off + k);
+      sc[i] = *(const bf16x8*)(md + a.xf.scale_off + k);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  first();
+  __builtin_amdgcn_sched_barrier(0);
+  if (wave < a.M) {
+    // the DMA is older than 3 * IPR operand loads and the weight loads
+    constexpr int after = 3 * IPR + U;
+    __builtin_amdgcn_s_waitcnt((after & 15) | ((after >> 4) << 14) | (7 << 4) | (15 << 8));
+    bf16x8 xv[IPR];
+#pragma unroll
+    for (int i = 0; i < IPR; ++i) xv[i] = *(const bf16x8*)(xrow_l + (lane + 64 * i) * 8);
+    rw_row_norm<IPR, true>(a, g, xv, wv, sc, sh, has_w, true, true, xrow_l);
+  }
+}
+// XF_ATTN_MERGE: o_proj's A rows = the decode attention output, merged from the
+// key splits' partials k_attn left (AttnArgs::defer, or its groups' partials): the
+// attention kernel's own merge (attn_dev.h attn_merge_parts, so bit-identical),
+// one round trip of partial loads here instead of a ticket + merge at the
+// attention's tail.  Item (m, 8 dims of head hq).
+template <class F>
+DEV void gemv1_stage_merge(const GemmArgs& a, const Gemv1Geo& g, F first) {
+  const int n8 = g.n8, nsp = a.xf.nsplit;
+  // the weight stream first: the merge's two dependent round trips (query
+  // length, then the partials) then overlap it instead of preceding it
+  first();
+#pragma unroll 1
+  for (int e = threadIdx.x; e < a.M * n8; e += g.NT) {
+    const int m = e / n8, k = (e - m * n8) * 8;
+    const int hq = k >> 7, j0 = k & 127;
+    const int np = attn_row_splits(a.xf.qpos[m] + 1, nsp, a.xf.chunk, 0).nact;
+    const long long p0 = ((long long)m * (a.K >> 7) + hq) * nsp;
+    float M, num[8], den;
+    attn_merge_parts<8>(
+        np,
+        [&](int s, float& ms, float& ls, float(&os)[8]) __attribute__((always_inline)) {
+          const float2 ml = *(const float2*)(a.xf.part_ml + (p0 + s) * 2);
+          ms = ml.x;
+          ls = ml.y;
+          const f32x4 o0 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0);
+          const f32x4 o1 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0 + 4);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            os[q] = o0[q];
+            os[4 + q] = o1[q];
+          }
+        },
+        M, num, den);
+    bf16x8 o8;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) o8[jj] = tobf(num[jj] / den);
+    *(bf16x8*)(g.xs + m * g.lds_ld + k) = o8;
+  }
+}
+// XF_MIX: the codec Block1D front half for the M = ns * T rows (codec_dev.h's
+// arithmetic, a row's chunk sums added in k_mix's order): every workgroup
+// recomputes it (a few tens of KB of L2 reads next to its weight slice);
+// workgroup 0 also stores the conv-buffer rows and y.  One dependent global
+// round trip: operands, x rows and history rows are issued together ahead of
+// the weight stream (the slot ids come through the scalar cache: sbase, read
+// by the kernel before any store), the raw x rows stay in LDS (xs) and are
+// overwritten by y, then by fc1's normalised input.
+template <class F>
+DEV void gemv1_stage_mix(const GemmArgs& a, const Gemv1Geo& g, long long sb0, long long sb1, long long sb2, long long sb3,
+                         F first) {
+  const long long sbase[4] = {sb0, sb1, sb2, sb3};   // by value: through a reference the selects below became a scratch array
+  const int NT = g.NT, n8 = g.n8, lds_ld = g.lds_ld;
+  bf16* xs = g.xs;
+  float* inv_s = g.inv_s;
+  const int C = a.K, T = a.xf.T, ctx = a.xf.ctx, ns = a.M / T;
+  bf16* nrm = (bf16*)g.part;                               // [ns][ctx + T][C] conv input rows
+  float* ssp = (float*)(nrm + (size_t)ns * (ctx + T) * C); // [M][n8] partial sums of squares
+  const bool writer = blockIdx.x == 0;
+  const int c2 = threadIdx.x % n8;                         // fixed: NT % n8 == 0
+  bf16x8 wk[7], bb, gv, wf, wn;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) wk[k] = *(const bf16x8*)(a.xf.dw_w + (size_t)c2 * 56 + k * 8);
+  bb = *(const bf16x8*)(a.xf.dw_b + c2 * 8);
+  gv = *(const bf16x8*)(a.xf.gamma + c2 * 8);
+  wf = *(const bf16x8*)(a.xf.ffn_w + c2 * 8);
+  wn = *(const bf16x8*)(a.xf.w + c2 * 8);
+  // items [0, M*n8): x row m; [M*n8, (M + ns*ctx)*n8): history row h of sample s.
+  // Every load is unconditional from an address chosen by selects (items past
+  // the end re-read the last one): guarded loads, and rm_off's optional slot
+  // lookup, compiled to a branch + s_waitcnt vmcnt(0) per item -- eight
+  // serialized round trips per pass.  (x rows: host-checked plain map, no idx.)
+  // Rows, not items: the n8 consecutive threads of a row share it, so thread t
+  // takes rows t / n8 + j * (NT / n8) -- no per-item division (the item form
+  // spent ~100 VALU per item on index math ahead of the weight stream).
+  constexpr int CTX = 6;                                    // host-checked (k = 7)
+  const int nrow = a.M + ns * CTX, rpt = NT / n8, rt = threadIdx.x / n8, nx = a.M * n8;
+  const bf16* xbase = (const bf16*)a.a.base;
+  for (int r0 = 0, it0 = 1; r0 < nrow; r0 += 8 * rpt, it0 = 0) {
+    bf16x8 v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int R = min(r0 + rt + q * rpt, nrow - 1);
+      const int mx = min(R, a.M - 1), gx = mx / a.a.T;
+      const bf16* px = xbase + gx * a.a.sB + (long long)(mx - gx * a.a.T) * a.a.sT;
+      const int hr = max(R - a.M, 0), s_ = hr / CTX;
+      long long sb = sbase[0];
+#pragma unroll
+      for (int q2 = 1; q2 < 4; ++q2) sb = s_ == q2 ? sbase[q2] : sb;
+      const bf16* ph = a.xf.buf + sb + (long long)(hr - s_ * CTX) * C;
+      v[q] = *(const bf16x8*)((R < a.M ? px : ph) + c2 * 8);
+    }
+    if (it0) first();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int R = r0 + rt + q * rpt;
+      if (R < a.M) {
+        *(bf16x8*)(xs + R * lds_ld + c2 * 8) = v[q];
+        ssp[R * n8 + c2] = cb_ss8(v[q]);
+      } else if (R < nrow) {
+        const int hr = R - a.M, s_ = hr / CTX;
+        *(bf16x8*)(nrm + ((size_t)s_ * (CTX + T) + (hr - s_ * CTX)) * C + c2 * 8) = v[q];
+      }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  part_inv(ssp, n8, a.M, C, a.xf.eps, inv_s, g.wave, g.NW, g.lane);   // k_mix's row-sum order (64 lanes)
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // mixer norm of the new rows -> conv input rows; workgroup 0 appends them to the buffer
+  for (int e = threadIdx.x; e < nx; e += NT) {
+    const int m = e / n8, s_ = m / T, t = m - s_ * T;
+    const bf16x8 v = *(const bf16x8*)(xs + m * lds_ld + c2 * 8);
+    const float rr = inv_s[m];
+    bf16x8 o8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o8[j] = cb_norm(v[j], rr, wn[j]);
+    *(bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + ctx + t) * C + c2 * 8) = o8;
+    if (writer) {
+      long long sb = sbase[0];
+#pragma unroll
+      for (int q2 = 1; q2 < 4; ++q2) sb = s_ == q2 ? sbase[q2] : sb;
+      *(bf16x8*)(a.xf.buf + sb + (long long)(ctx + t) * C + c2 * 8) = o8;
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // depthwise conv + gamma residual: y over the raw x in xs (workgroup 0 stores y)
+  for (int e = threadIdx.x; e < nx; e += NT) {
+    const int m = e / n8, s_ = m / T, t = m - s_ * T;
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+      cb_conv8(acc, wk, *(const bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + t + k) * C + c2 * 8), k);
+    bf16x8* px = (bf16x8*)(xs + m * lds_ld + c2 * 8);
+    const bf16x8 xv = *px;
+    bf16x8 y8;
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      y8[j] = cb_y(xv[j], acc[j], bb[j], gv[j]);
+      ss += bf(y8[j]) * bf(y8[j]);
+    }
+    if (writer) *(bf16x8*)(a.xf.y + (long long)m * C + c2 * 8) = y8;
+    *px = y8;
+    ssp[e] = ss;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  part_inv(ssp, n8, a.M, C, a.xf.eps, inv_s, g.wave, g.NW, g.lane);
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  for (int e = threadIdx.x; e < nx; e += NT) {             // FFN pre-norm, in place
+    const int m = e / n8;
+    bf16x8* px = (bf16x8*)(xs + m * lds_ld + c2 * 8);
+    const bf16x8 y8 = *px;
+    const float rr = inv_s[m];
+    bf16x8 o8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o8[j] = cb_norm(y8[j], rr, wf[j]);
+    *px = o8;
+  }
+}
+// The item-per-thread "fast" form (g.fast): every item (row m, 8 columns) of
+// the block in one batch of GEMV1_Q registers per thread.  Every A-side load is
+// unconditional (items past the end re-read the last; absent operands re-read
+// the row) and, for a plain row map, has no slot lookup: a guarded load
+// compiled to a branch + s_waitcnt vmcnt(0) at its join, so each item waited
+// for the one before it and the weight stream behind them was issued several
+// round trips late.
+template <int XF, class F>
+DEV void gemv1_stage_fast(const GemmArgs& a, const Gemv1Geo& g, F first) {
+  constexpr int Q = GEMV1_Q;
+  const int NT = g.NT, n8 = g.n8, b0 = g.b0;
+  bf16x8 xv[Q], wv[Q], sh[Q], sc[Q];
+  const int ne = a.M * n8;
+  const bool has_w = XF == XF_NORM ? a.xf.w != nullptr : XF == XF_SILU_ADD;
+  const bool has_mod = XF == XF_NORM && a.xf.mod != nullptr;
+  auto fast_loads = [&](auto plain_c) {
+    constexpr bool PLAIN = decltype(plain_c)::value;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int e = min(threadIdx.x + q * NT, ne - 1);
+      const int m = e / n8, k = b0 * 32 + (e - m * n8) * 8;
+      const bf16* xr = PLAIN ? rm_bf_plain(a.a, m) : rm_bf(a.a, m);
+      xv[q] = *(const bf16x8*)(xr + k);
+      if (XF == XF_NORM || XF == XF_SILU_ADD) {
+        const bf16* wp = has_w ? (XF == XF_NORM ? a.xf.w : a.xf.vec) : xr;
+        wv[q] = *(const bf16x8*)(wp + k);
+      }
+      if (XF == XF_NORM) {
+        const bf16* md = has_mod ? a.xf.mod + (long long)m * a.xf.mod_ld : xr;
+        sh[q] = *(const bf16x8*)(md + (has_mod ? a.xf.shift_off : 0) + k);
+        sc[q] = *(const bf16x8*)(md + (has_mod ? a.xf.scale_off : 0) + k);
+      }
+    }
+  };
+  if (a.a.idx) fast_loads(std::false_type());
+  else fast_loads(std::true_type());
+  first();
+  if (XF == XF_NORM) {
+    // per-item sums of squares -> LDS, rows reduced in a fixed order
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int e = threadIdx.x + q * NT;
+      if (e < a.M * n8) g.part[e] = ss8(xv[q]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (a.ksplit == 1) part_inv(g.part, n8, a.M, a.K, a.xf.eps, g.inv_s, g.wave, g.NW, g.lane);
+    else row_inv(a, 0, a.M, g.inv_s, g.wave, g.NW, g.lane);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int e = threadIdx.x + q * NT;
+    if (e < a.M * n8) {
+      const int m = e / n8, k8 = (e - m * n8) * 8;
+      bf16x8 o = xv[q];
+      if (XF == XF_NORM) {
+        const float inv = g.inv_s[m];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          o[j] = norm_rt(xv[q][j], inv, a.xf.w != nullptr, wv[q][j], a.xf.mod != nullptr, sc[q][j], sh[q][j]);
+      } else if (XF == XF_SILU_ADD) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = tobf(silu_f(rb(bf(xv[q][j]) + bf(wv[q][j]))));
+      }
+      *(bf16x8*)(g.xs + m * g.lds_ld + k8) = o;
+    }
+  }
+}
+// The many-rows "staged" form (B >= 8 batches): weights first, then the A rows
+// through registers to LDS in batches of 4 items per thread; the transform runs
+// on the LDS rows (a row's sum of squares: ss8_run over its lanes' items).
+template <int XF, class F>
+DEV void gemv1_stage_rows(const GemmArgs& a, const Gemv1Geo& g, F first) {
+  const int NT = g.NT, NW = g.NW, lane = g.lane, wave = g.wave, n8 = g.n8, lds_ld = g.lds_ld, b0 = g.b0;
+  bf16* xs = g.xs;
+  float* inv_s = g.inv_s;
+  first();
+  const int ne = a.M * n8;
+  const bool plain = !a.a.idx;
+  for (int e0 = threadIdx.x; e0 < ne; e0 += 4 * NT) {
+    bf16x8 xv[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {   // unconditional loads (see the fast form)
+      const int e = min(e0 + q * NT, ne - 1);
+      const int m = e / n8, k8 = (e - m * n8) * 8;
+      xv[q] = *(const bf16x8*)((plain ? rm_bf_plain(a.a, m) : rm_bf(a.a, m)) + b0 * 32 + k8);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int e = e0 + q * NT;
+      if (e < a.M * n8) {
+        const int m = e / n8, k8 = (e - m * n8) * 8;
+        *(bf16x8*)(xs + m * lds_ld + k8) = xv[q];
+      }
+    }
+  }
+  if (XF != XF_NONE) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (XF == XF_NORM) {
+      if (a.ksplit == 1) {
+        for (int m = wave; m < a.M; m += NW) {
+          float ss = 0.f;
+          for (int c = lane; c < n8; c += 64) ss = ss8_run(ss, *(const bf16x8*)(xs + m * lds_ld + c * 8));
+          ss = wave_sum(ss);
+          if (lane == 0) inv_s[m] = rsqrtf(ss / (float)a.K + a.xf.eps);
+        }
+      } else {
+        row_inv(a, 0, a.M, inv_s, wave, NW, lane);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+    for (int e = threadIdx.x; e < a.M * n8; e += NT) {
+      const int m = e / n8, k8 = (e - m * n8) * 8;
+      bf16x8* px = (bf16x8*)(xs + m * lds_ld + k8);
+      *px = xform<XF>(a, *px, m, b0 * 32 + k8, XF == XF_NORM ? inv_s[m] : 0.f);
+    }
+  }
+}
+
+// k_gemv1: geometry; stage A while the first weight batch is in flight; barrier;
+// stream; reduce; epilogue.
 template <int U, int XF, bool KEEP = false, int TPW = 1, int RW = 0>
 __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -161,467 +560,47 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
   const int ntl = TPW == 1 ? 1 : part_of(ntile, blockIdx.x + 1, gridDim.x) - T0;
   const int tile = T0 + tw;
   const bool tile_ok = TPW == 1 || tw < ntl;
-  const int nchunk = a.K >> 5;
-  // this workgroup's chunk range, then each wave's
-  const int b0 = a.ksplit == 1 ? 0 : part_of(nchunk, blockIdx.y, a.ksplit);
-  const int b1 = a.ksplit == 1 ? nchunk : part_of(nchunk, blockIdx.y + 1, a.ksplit);
-  const int c0 = b0 + part_of(b1 - b0, kwv, KW);
-  const int c1 = tile_ok ? b0 + part_of(b1 - b0, kwv + 1, KW) : c0;
+  // this workgroup's chunk range [b0, b1), then the wave's [c0, c1)
+  const KRange kr = k_range(a.K >> 5, a.ksplit, kwv, KW);
+  const int b0 = kr.b0, b1 = kr.b1, c0 = kr.c0, c1 = tile_ok ? kr.c1 : c0;
   // MFMA-packed W (a wave past the last tile streams nothing; its clamped
   // prologue loads read tile 0)
   const bf16* wrow = a.w + (long long)(tile_ok ? tile : 0) * a.K * 16 + lane * 8;
   const bf16x8 zero8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-
-  // ---- A staging into LDS (rows [0, M) x chunks [b0, b1), row stride padded
-  // 16 B), overlapped with the first weight chunks.  vmcnt waits are in issue
-  // order, so every A-side load (row chunk + its transform operands) is issued
-  // BEFORE the weight loads: the prologue then waits only for its own bytes and
-  // the weight stream stays in flight through the norm math.
-  const int kw = (b1 - b0) * 32;         // elements staged per row
-  const int lds_ld = kw + 8;
-  const int n8 = kw >> 3;
-  bf16* xs = (bf16*)smem;
-  float* part = (float*)(smem + (((size_t)a.M * lds_ld * 2 + 15) & ~(size_t)15));
   bf16x8 wa[U], wb[U];
-  constexpr int Q = 4;   // A items per thread on the fast path
-  const bool fast = a.M * n8 <= Q * NT;
-  // row-per-wave norm prologue: items per lane per row (IPR) x rows per wave (RPW)
-  // (RW instantiations only; the host picks them for eligible shapes, gemm_decide)
-  const int ipr = n8 >> 6, rpw = (a.M + NW - 1) / NW;
-  const int rw = ipr == 3 && rpw == 1 ? 31 : ipr == 3 ? 32 : 71;
-  // whole rows per wave: loads (A, norm weight, adaLN shift / scale; all
-  // unconditional, clamped to valid rows, so no branch join waits on them),
-  // then the weight stream, then sums, wave_sum and the norm in registers
-  auto stage_rw = [&](auto ipr_c, auto rpw_c, auto mod_c) {
-    constexpr int IPR = decltype(ipr_c)::value, RPW = decltype(rpw_c)::value, QR = IPR * RPW;
-    constexpr bool MOD = decltype(mod_c)::value;   // adaLN operands possible (their registers reserved)
-    bf16x8 xv[QR], wv[QR], sh[MOD ? QR : 1], sc[MOD ? QR : 1];
-    const bool has_w = a.xf.w != nullptr, has_mod = MOD && a.xf.mod != nullptr;
+  auto load = [&](bf16x8 (&wf)[U], int c) {
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const int m = min(wave * RPW + r, a.M - 1);
-      const bf16* xr = rm_bf(a.a, m);
-      const bf16* wp = has_w ? a.xf.w : xr;
-      const bf16* md = has_mod ? a.xf.mod + (long long)m * a.xf.mod_ld : xr;
-      const int so = has_mod ? a.xf.shift_off : 0, co = has_mod ? a.xf.scale_off : 0;
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) {
-        const int k = (lane + 64 * i) * 8;
-        xv[r * IPR + i] = *(const bf16x8*)(xr + k);
-        wv[r * IPR + i] = *(const bf16x8*)(wp + k);
-        if (has_mod) {
-          sh[MOD ? r * IPR + i : 0] = *(const bf16x8*)(md + so + k);
-          sc[MOD ? r * IPR + i : 0] = *(const bf16x8*)(md + co + k);
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) {
-        if (fast) {   // the item-per-thread fast form: per-item partials, then items in order
-          float p = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) p += bf(xv[r * IPR + i][j]) * bf(xv[r * IPR + i][j]);
-          ss += p;
-        } else {      // the staged form / k_rmsnorm: one running sum
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ss += bf(xv[r * IPR + i][j]) * bf(xv[r * IPR + i][j]);
-        }
-      }
-      ss = wave_sum(ss);
-      const float inv = rsqrtf(ss / (float)a.K + a.xf.eps);
-      const int m = wave * RPW + r;
-      // (the uniform has_w / has_mod tests stay per element: hoisting them into
-      // specialised copies raised the kernel to 180 VGPRs, 3 -> 2 waves / SIMD)
-      if (m < a.M) {
-#pragma unroll
-        for (int i = 0; i < IPR; ++i) {
-          const int q = r * IPR + i;
-          bf16x8 o;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float t = rb(bf(xv[q][j]) * inv);
-            if (has_w) t = rb(t * bf(wv[q][j]));
-            if (has_mod) t = rb(rb(t * rb(1.0f + bf(sc[MOD ? q : 0][j]))) + bf(sh[MOD ? q : 0][j]));
-            o[j] = tobf(t);
-          }
-          *(bf16x8*)(xs + m * lds_ld + (lane + 64 * i) * 8) = o;
-        }
-      }
-    }
+    for (int u = 0; u < U; ++u) wf[u] = ldw<KEEP>(wrow + min(c + u, max(c1 - 1, 0)) * 512);
   };
-  // K = 3,584 rows with adaLN operands (VibeVoice-Large head): the raw A row
-  // goes straight to its LDS row by 16-byte LDS DMA (lane l's item i lands at
-  // (l + 64 i) * 8, the row layout), so only the norm weight and shift / scale
-  // take registers; the row is read back by its own lanes after a counted vmcnt
-  // (the 21 operand loads and the U weight loads issued after it stay in flight)
-  auto stage_rw_dma = [&]() {
-    constexpr int IPR = 7;
-    bf16x8 wv[IPR], sh[IPR], sc[IPR];
-    const bool has_w = a.xf.w != nullptr;
-    const int m = min(wave, a.M - 1);
-    bf16* xrow_l = xs + m * lds_ld;
-    if (wave < a.M) {
-      const bf16* xr = rm_bf(a.a, m);
-      const bf16* wp = has_w ? a.xf.w : xr;
-      const bf16* md = a.xf.mod + (long long)m * a.xf.mod_ld;
-#pragma unroll
-      for (int i = 0; i < IPR; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)(xr + (lane + 64 * i) * 8),
-                                         (__attribute__((address_space(3))) void*)(xrow_l + 64 * i * 8), 16, 0, 0);
-      // the counted wait below needs exactly these loads younger than the DMA,
-      // in this order: sched_barrier fences keep the scheduler from moving any
-      // of them across
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) {
-        const int k = (lane + 64 * i) * 8;
-        wv[i] = *(const bf16x8*)(wp + k);
-        sh[i] = *(const bf16x8*)(md + a.xf.shift_off + k);
-        sc[i] = *(const bf16x8*)(md + a.xf.scale_off + k);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-    __builtin_amdgcn_sched_barrier(0);
-    if (wave < a.M) {
-      // the DMA is older than 3 * IPR operand loads and the weight loads
-      constexpr int after = 3 * IPR + U;
-      __builtin_amdgcn_s_waitcnt((after & 15) | ((after >> 4) << 14) | (7 << 4) | (15 << 8));
-      bf16x8 xv[IPR];
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) xv[i] = *(const bf16x8*)(xrow_l + (lane + 64 * i) * 8);
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) {
-        if (fast) {
-          float p = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) p += bf(xv[i][j]) * bf(xv[i][j]);
-          ss += p;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ss += bf(xv[i][j]) * bf(xv[i][j]);
-        }
-      }
-      ss = wave_sum(ss);
-      const float inv = rsqrtf(ss / (float)a.K + a.xf.eps);
-#pragma unroll
-      for (int i = 0; i < IPR; ++i) {
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float t = rb(bf(xv[i][j]) * inv);
-          if (has_w) t = rb(t * bf(wv[i][j]));
-          t = rb(rb(t * rb(1.0f + bf(sc[i][j]))) + bf(sh[i][j]));
-          o[j] = tobf(t);
-        }
-        *(bf16x8*)(xrow_l + (lane + 64 * i) * 8) = o;
-      }
-    }
-  };
+  auto first = [&]() { load(wa, c0); };
+
+  // ---- A staging (the gemv1_stage_* forms above), the first weight batch issued inside it
+  const int kw = (b1 - b0) * 32;         // elements staged per row
+  Gemv1Geo geo;
+  geo.NT = NT, geo.NW = NW, geo.lane = lane, geo.wave = wave, geo.b0 = b0;
+  geo.n8 = kw >> 3, geo.lds_ld = kw + 8;
+  geo.fast = a.M * geo.n8 <= GEMV1_Q * NT;
+  geo.xs = (bf16*)smem;
+  geo.part = (float*)(smem + (((size_t)a.M * geo.lds_ld * 2 + 15) & ~(size_t)15));
+  geo.inv_s = inv_s;
+  const int lds_ld = geo.lds_ld;
+  const bf16* xs = geo.xs;
   if constexpr (RW == 2) {   // its own instantiation: its registers would cost the others occupancy
-    stage_rw_dma();
+    gemv1_stage_rw_dma<U>(a, geo, first);
   } else if constexpr (RW == 1) {
-    using I = std::true_type;
-    if (rw == 31) stage_rw(std::integral_constant<int, 3>(), std::integral_constant<int, 1>(), I());
-    else if (rw == 32) stage_rw(std::integral_constant<int, 3>(), std::integral_constant<int, 2>(), I());
-    else stage_rw(std::integral_constant<int, 7>(), std::integral_constant<int, 1>(), std::false_type());
-  } else if (XF == XF_ATTN_MERGE) {
-    // o_proj's A rows = the decode attention output, merged from the key splits'
-    // partials k_attn left (AttnArgs::defer, or its groups' partials): the
-    // attention kernel's own merge (attn_dev.h attn_merge_parts, so bit-identical),
-    // one round trip of partial loads here instead of a ticket + merge at the
-    // attention's tail.  Item (m, 8 dims of head hq).
-    const int nsp = a.xf.nsplit;
-    // the weight stream first: the merge's two dependent round trips (query
-    // length, then the partials) then overlap it instead of preceding it
-#pragma unroll
-    for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-#pragma unroll 1
-    for (int e = threadIdx.x; e < a.M * n8; e += NT) {
-      const int m = e / n8, k = (e - m * n8) * 8;
-      const int hq = k >> 7, j0 = k & 127;
-      const int np = attn_row_splits(a.xf.qpos[m] + 1, nsp, a.xf.chunk, 0).nact;
-      const long long p0 = ((long long)m * (a.K >> 7) + hq) * nsp;
-      float M, num[8], den;
-      attn_merge_parts<8>(
-          np,
-          [&](int s, float& ms, float& ls, float(&os)[8]) __attribute__((always_inline)) {
-            const float2 ml = *(const float2*)(a.xf.part_ml + (p0 + s) * 2);
-            ms = ml.x;
-            ls = ml.y;
-            const f32x4 o0 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0);
-            const f32x4 o1 = *(const f32x4*)(a.xf.part_o + (p0 + s) * 128 + j0 + 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              os[q] = o0[q];
-              os[4 + q] = o1[q];
-            }
-          },
-          M, num, den);
-      bf16x8 o8;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) o8[jj] = tobf(num[jj] / den);
-      *(bf16x8*)(xs + m * lds_ld + k) = o8;
-    }
-  } else if (XF == XF_MIX) {
-    // Codec Block1D front half for the M = ns * T rows (codec_dev.h's arithmetic,
-    // a row's chunk sums added in k_mix's order): every workgroup recomputes it (a few
-    // tens of KB of L2 reads next to its weight slice); workgroup 0 also stores
-    // the conv-buffer rows and y.  One dependent global round trip: operands,
-    // x rows and history rows are issued together ahead of the weight stream
-    // (the slot ids come through the scalar cache), the raw x rows stay in LDS
-    // (xs) and are overwritten by y, then by fc1's normalised input.
-    const int C = a.K, T = a.xf.T, ctx = a.xf.ctx, ns = a.M / T;
-    bf16* nrm = (bf16*)part;                                 // [ns][ctx + T][C] conv input rows
-    float* ssp = (float*)(nrm + (size_t)ns * (ctx + T) * C); // [M][n8] partial sums of squares
-    const bool writer = blockIdx.x == 0;
-    const int c2 = threadIdx.x % n8;                         // fixed: NT % n8 == 0
-    bf16x8 wk[7], bb, gv, wf, wn;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) wk[k] = *(const bf16x8*)(a.xf.dw_w + (size_t)c2 * 56 + k * 8);
-    bb = *(const bf16x8*)(a.xf.dw_b + c2 * 8);
-    gv = *(const bf16x8*)(a.xf.gamma + c2 * 8);
-    wf = *(const bf16x8*)(a.xf.ffn_w + c2 * 8);
-    wn = *(const bf16x8*)(a.xf.w + c2 * 8);
-    // items [0, M*n8): x row m; [M*n8, (M + ns*ctx)*n8): history row h of sample s.
-    // Every load is unconditional from an address chosen by selects (items past
-    // the end re-read the last one): guarded loads, and rm_off's optional slot
-    // lookup, compiled to a branch + s_waitcnt vmcnt(0) per item -- eight
-    // serialized round trips per pass.  (x rows: host-checked plain map, no idx.)
-    // Rows, not items: the n8 consecutive threads of a row share it, so thread t
-    // takes rows t / n8 + j * (NT / n8) -- no per-item division (the item form
-    // spent ~100 VALU per item on index math ahead of the weight stream).
-    constexpr int CTX = 6;                                    // host-checked (k = 7)
-    const int nrow = a.M + ns * CTX, rpt = NT / n8, rt = threadIdx.x / n8, nx = a.M * n8;
-    const bf16* xbase = (const bf16*)a.a.base;
-    for (int r0 = 0, first = 1; r0 < nrow; r0 += 8 * rpt, first = 0) {
-      bf16x8 v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int R = min(r0 + rt + q * rpt, nrow - 1);
-        const int mx = min(R, a.M - 1), gx = mx / a.a.T;
-        const bf16* px = xbase + gx * a.a.sB + (long long)(mx - gx * a.a.T) * a.a.sT;
-        const int hr = max(R - a.M, 0), s_ = hr / CTX;
-        long long sb = sbase[0];
-#pragma unroll
-        for (int q2 = 1; q2 < 4; ++q2) sb = s_ == q2 ? sbase[q2] : sb;
-        const bf16* ph = a.xf.buf + sb + (long long)(hr - s_ * CTX) * C;
-        v[q] = *(const bf16x8*)((R < a.M ? px : ph) + c2 * 8);
-      }
-      if (first) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int R = r0 + rt + q * rpt;
-        if (R < a.M) {
-          *(bf16x8*)(xs + R * lds_ld + c2 * 8) = v[q];
-          ssp[R * n8 + c2] = cb_ss8(v[q]);
-        } else if (R < nrow) {
-          const int hr = R - a.M, s_ = hr / CTX;
-          *(bf16x8*)(nrm + ((size_t)s_ * (CTX + T) + (hr - s_ * CTX)) * C + c2 * 8) = v[q];
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    for (int m = wave; m < a.M; m += NW) {                   // k_mix's row-sum order (64 lanes)
-      float ss = 0.f;
-      for (int c = lane; c < n8; c += 64) ss += ssp[m * n8 + c];
-      ss = wave_sum(ss);
-      if (lane == 0) inv_s[m] = rsqrtf(ss / (float)C + a.xf.eps);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // mixer norm of the new rows -> conv input rows; workgroup 0 appends them to the buffer
-    for (int e = threadIdx.x; e < nx; e += NT) {
-      const int m = e / n8, s_ = m / T, t = m - s_ * T;
-      const bf16x8 v = *(const bf16x8*)(xs + m * lds_ld + c2 * 8);
-      const float rr = inv_s[m];
-      bf16x8 o8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o8[j] = cb_norm(v[j], rr, wn[j]);
-      *(bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + ctx + t) * C + c2 * 8) = o8;
-      if (writer) {
-        long long sb = sbase[0];
-#pragma unroll
-        for (int q2 = 1; q2 < 4; ++q2) sb = s_ == q2 ? sbase[q2] : sb;
-        *(bf16x8*)(a.xf.buf + sb + (long long)(ctx + t) * C + c2 * 8) = o8;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // depthwise conv + gamma residual: y over the raw x in xs (workgroup 0 stores y)
-    for (int e = threadIdx.x; e < nx; e += NT) {
-      const int m = e / n8, s_ = m / T, t = m - s_ * T;
-      float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 7; ++k)
-        cb_conv8(acc, wk, *(const bf16x8*)(nrm + ((size_t)s_ * (ctx + T) + t + k) * C + c2 * 8), k);
-      bf16x8* px = (bf16x8*)(xs + m * lds_ld + c2 * 8);
-      const bf16x8 xv = *px;
-      bf16x8 y8;
-      float ss = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        y8[j] = cb_y(xv[j], acc[j], bb[j], gv[j]);
-        ss += bf(y8[j]) * bf(y8[j]);
-      }
-      if (writer) *(bf16x8*)(a.xf.y + (long long)m * C + c2 * 8) = y8;
-      *px = y8;
-      ssp[e] = ss;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    for (int m = wave; m < a.M; m += NW) {
-      float ss = 0.f;
-      for (int c = lane; c < n8; c += 64) ss += ssp[m * n8 + c];
-      ss = wave_sum(ss);
-      if (lane == 0) inv_s[m] = rsqrtf(ss / (float)C + a.xf.eps);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    for (int e = threadIdx.x; e < nx; e += NT) {             // FFN pre-norm, in place
-      const int m = e / n8;
-      bf16x8* px = (bf16x8*)(xs + m * lds_ld + c2 * 8);
-      const bf16x8 y8 = *px;
-      const float rr = inv_s[m];
-      bf16x8 o8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o8[j] = cb_norm(y8[j], rr, wf[j]);
-      *px = o8;
-    }
-  } else if (fast) {
-    bf16x8 xv[Q], wv[Q], sh[Q], sc[Q];
-    // every A-side load unconditional (items past the end re-read the last;
-    // absent operands re-read the row) and, for a plain row map, no slot
-    // lookup: a guarded load compiled to a branch + s_waitcnt vmcnt(0) at its
-    // join, so each item waited for the one before it and the weight stream
-    // behind them was issued several round trips late
-    const int ne = a.M * n8;
-    const bool has_w = XF == XF_NORM ? a.xf.w != nullptr : XF == XF_SILU_ADD;
-    const bool has_mod = XF == XF_NORM && a.xf.mod != nullptr;
-    auto fast_loads = [&](auto plain_c) {
-      constexpr bool PLAIN = decltype(plain_c)::value;
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const int e = min(threadIdx.x + q * NT, ne - 1);
-        const int m = e / n8, k = b0 * 32 + (e - m * n8) * 8;
-        const bf16* xr = PLAIN ? rm_bf_plain(a.a, m) : rm_bf(a.a, m);
-        xv[q] = *(const bf16x8*)(xr + k);
-        if (XF == XF_NORM || XF == XF_SILU_ADD) {
-          const bf16* wp = has_w ? (XF == XF_NORM ? a.xf.w : a.xf.vec) : xr;
-          wv[q] = *(const bf16x8*)(wp + k);
-        }
-        if (XF == XF_NORM) {
-          const bf16* md = has_mod ? a.xf.mod + (long long)m * a.xf.mod_ld : xr;
-          sh[q] = *(const bf16x8*)(md + (has_mod ? a.xf.shift_off : 0) + k);
-          sc[q] = *(const bf16x8*)(md + (has_mod ? a.xf.scale_off : 0) + k);
-        }
-      }
-    };
-    if (a.a.idx) fast_loads(std::false_type());
-    else fast_loads(std::true_type());
-#pragma unroll
-    for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-    if (XF == XF_NORM) {
-      // per-item sums of squares -> LDS, rows reduced in a fixed order
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const int e = threadIdx.x + q * NT;
-        if (e < a.M * n8) {
-          float ss = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) ss += bf(xv[q][j]) * bf(xv[q][j]);
-          part[e] = ss;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (a.ksplit == 1) {
-        for (int m = wave; m < a.M; m += NW) {
-          float ss = 0.f;
-          for (int c = lane; c < n8; c += 64) ss += part[m * n8 + c];
-          ss = wave_sum(ss);
-          if (lane == 0) inv_s[m] = rsqrtf(ss / (float)a.K + a.xf.eps);
-        }
-      } else {
-        row_inv(a, 0, a.M, inv_s, wave, NW, lane);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const int e = threadIdx.x + q * NT;
-      if (e < a.M * n8) {
-        const int m = e / n8, k8 = (e - m * n8) * 8;
-        bf16x8 o = xv[q];
-        if (XF == XF_NORM) {
-          const float inv = inv_s[m];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float t = rb(bf(xv[q][j]) * inv);
-            if (a.xf.w) t = rb(t * bf(wv[q][j]));
-            if (a.xf.mod) t = rb(rb(t * rb(1.0f + bf(sc[q][j]))) + bf(sh[q][j]));
-            o[j] = tobf(t);
-          }
-        } else if (XF == XF_SILU_ADD) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] = tobf(silu_f(rb(bf(xv[q][j]) + bf(wv[q][j]))));
-        }
-        *(bf16x8*)(xs + m * lds_ld + k8) = o;
-      }
-    }
+    // items per lane per row x rows per wave (the host picks RW for eligible shapes, gemm_decide)
+    const int ipr = geo.n8 >> 6, rpw = (a.M + NW - 1) / NW;
+    if (ipr == 3 && rpw == 1) gemv1_stage_rw<3, 1, true>(a, geo, first);
+    else if (ipr == 3) gemv1_stage_rw<3, 2, true>(a, geo, first);
+    else gemv1_stage_rw<7, 1, false>(a, geo, first);
+  } else if constexpr (XF == XF_ATTN_MERGE) {
+    gemv1_stage_merge(a, geo, first);
+  } else if constexpr (XF == XF_MIX) {
+    gemv1_stage_mix(a, geo, sbase[0], sbase[1], sbase[2], sbase[3], first);
+  } else if (geo.fast) {
+    gemv1_stage_fast<XF>(a, geo, first);
   } else {
-    // many rows (B >= 8 batches): weights first, then the A rows in batches
-#pragma unroll
-    for (int u = 0; u < U; ++u) wa[u] = ldw<KEEP>(wrow + min(c0 + u, max(c1 - 1, 0)) * 512);
-    const int ne = a.M * n8;
-    const bool plain = !a.a.idx;
-    for (int e0 = threadIdx.x; e0 < ne; e0 += 4 * NT) {
-      bf16x8 xv[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {   // unconditional loads (see the fast path)
-        const int e = min(e0 + q * NT, ne - 1);
-        const int m = e / n8, k8 = (e - m * n8) * 8;
-        xv[q] = *(const bf16x8*)((plain ? rm_bf_plain(a.a, m) : rm_bf(a.a, m)) + b0 * 32 + k8);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int e = e0 + q * NT;
-        if (e < a.M * n8) {
-          const int m = e / n8, k8 = (e - m * n8) * 8;
-          *(bf16x8*)(xs + m * lds_ld + k8) = xv[q];
-        }
-      }
-    }
-    if (XF != XF_NONE) {
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (XF == XF_NORM) {
-        if (a.ksplit == 1) {
-          for (int m = wave; m < a.M; m += NW) {
-            float ss = 0.f;
-            for (int c = lane; c < n8; c += 64) {
-              const bf16x8 v = *(const bf16x8*)(xs + m * lds_ld + c * 8);
-#pragma unroll
-              for (int j = 0; j < 8; ++j) ss += bf(v[j]) * bf(v[j]);
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) inv_s[m] = rsqrtf(ss / (float)a.K + a.xf.eps);
-          }
-        } else {
-          row_inv(a, 0, a.M, inv_s, wave, NW, lane);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-      for (int e = threadIdx.x; e < a.M * n8; e += NT) {
-        const int m = e / n8, k8 = (e - m * n8) * 8;
-        bf16x8* px = (bf16x8*)(xs + m * lds_ld + k8);
-        *px = xform<XF>(a, *px, m, b0 * 32 + k8, XF == XF_NORM ? inv_s[m] : 0.f);
-      }
-    }
+    gemv1_stage_rows<XF>(a, geo, first);
   }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   stamp(a, 1);
@@ -642,10 +621,6 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
       acc = mfma(w, x[u], acc);
     }
   };
-  auto load = [&](bf16x8 (&wf)[U], int c) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) wf[u] = ldw<KEEP>(wrow + min(c + u, max(c1 - 1, 0)) * 512);
-  };
   for (int c = c0; c < c1; c += 2 * U) {
     load(wb, c + U);
     compute(wa, c);
@@ -658,15 +633,7 @@ __global__ void __launch_bounds__(64 * gemv1_max_waves(TPW)) k_gemv1(GemmArgs a)
 #pragma unroll
   for (int i = 0; i < 4; ++i) red[(wave * 4 + i) * 64 + lane] = acc[i];
   __syncthreads();
-  if (KW > 1) {
-    for (int e = threadIdx.x; e < TPW * 256; e += NT) {
-      const int base = (e >> 8) * KW * 256 + (e & 255);
-      float s = 0.f;
-      for (int w = 1; w < KW; ++w) s += red[base + w * 256];
-      red[base] += s;
-    }
-    __syncthreads();
-  }
+  slices_sum<TPW, 256>(red, KW, NT);
   if (a.ksplit > 1 && !splitk_handoff(a, red, 256, &last_flag, NT)) return;   // host: ksplit > 1 => TPW == 1
   if (wave < TPW && (TPW == 1 || wave < ntl)) {
     float v[4];
@@ -698,11 +665,8 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int nchunk = a.K >> 5;
-  const int b0 = a.ksplit == 1 ? 0 : part_of(nchunk, blockIdx.y, a.ksplit);
-  const int b1 = a.ksplit == 1 ? nchunk : part_of(nchunk, blockIdx.y + 1, a.ksplit);
-  const int c0 = b0 + part_of(b1 - b0, wave, NW);
-  const int c1 = b0 + part_of(b1 - b0, wave + 1, NW);
+  const KRange kr = k_range(a.K >> 5, a.ksplit, wave, NW);
+  const int c0 = kr.c0, c1 = kr.c1;
   const bf16* wrow = a.w + (long long)(n0 >> 4) * a.K * 16 + lane * 8;  // MFMA-packed W
   const unsigned char* wrow8 = a.w8 + (long long)(n0 >> 4) * a.K * 16 + lane * 16;   // W8: its codes
   const float wsc = W8 ? w8_scale(a.w8e[n0 + r]) : 0.f;
@@ -780,14 +744,7 @@ __global__ void __launch_bounds__(512) k_gemv(GemmArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) red[(wave * MREP * 4 + mr * 4 + i) * 64 + lane] = acc[mr][i];
   __syncthreads();
-  if (NW > 1) {
-    for (int e = threadIdx.x; e < TILE; e += NT) {
-      float s = 0.f;
-      for (int w = 1; w < NW; ++w) s += red[w * TILE + e];
-      red[e] += s;
-    }
-    __syncthreads();
-  }
+  slices_sum<1, TILE>(red, NW, NT);
   if (a.ksplit > 1 && !splitk_handoff(a, red, TILE, &last_flag, NT)) return;
   for (int mr = wave; mr < MREP; mr += NW) {
     float v[4];

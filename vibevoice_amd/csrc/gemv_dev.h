@@ -92,7 +92,67 @@ DEV f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// ------------------------------------------------------------------ K ranges
+// Index math of the GEMV prologues.  blockDim.x is a 16-bit implicit kernel
+// argument; gfx950 has no 16-bit scalar load, so a read of it that the
+// compiler cannot prove unclobbered (any global store earlier in the kernel,
+// e.g. a timing stamp) becomes a VECTOR load + s_waitcnt vmcnt(0): a whole
+// memory round trip before the first A / weight load was issued.  Kernels read
+// it once, first (a scalar load), and the K ranges use 32-bit arithmetic (the
+// 64-bit divisions were ~300 VALU instructions ahead of the first load).
+DEV int part_of(int len, int i, int n) { return (int)((unsigned)(len * i) / (unsigned)n); }
+// Units (32-column chunks, or chunk pairs) [b0, b1) of a workgroup and
+// [c0, c1) of its K slice kw of KW (a wave, or the waves of one tile)
+struct KRange {
+  int b0, b1, c0, c1;
+};
+DEV KRange k_slice(int b0, int b1, int kw, int KW) {
+  return {b0, b1, b0 + part_of(b1 - b0, kw, KW), b0 + part_of(b1 - b0, kw + 1, KW)};
+}
+// the workgroup's range = split blockIdx.y of ksplit cross-workgroup K splits
+DEV KRange k_range(int nunit, int ksplit, int kw, int KW) {
+  const int b0 = ksplit == 1 ? 0 : part_of(nunit, blockIdx.y, ksplit);
+  const int b1 = ksplit == 1 ? nunit : part_of(nunit, blockIdx.y + 1, ksplit);
+  return k_slice(b0, b1, kw, KW);
+}
+// The K-slice partial tiles red[slice][TILE] of NG groups of KW slices each
+// (group-major), summed into each group's slice 0: slices 1 .. KW-1 in order
+// into a sum from zero, then added to slice 0 (k_gemv1, k_gemv; k_gemvw and
+// k_gemv_w8 sum in other orders, which are theirs to keep).
+template <int NG, int TILE>
+DEV void slices_sum(float* red, int KW, int NT) {
+  if (KW > 1) {
+    for (int e = threadIdx.x; e < NG * TILE; e += NT) {
+      const int base = NG == 1 ? e : (int)((unsigned)e / TILE) * KW * TILE + (int)((unsigned)e % TILE);
+      float s = 0.f;
+      for (int w = 1; w < KW; ++w) s += red[base + w * TILE];
+      red[base] += s;
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------ A transform
+// Sum of squares of 8 elements of a row, in the two orders a row can be summed:
+//   ss8:     the 8 squares from zero (a per-item partial; a row adds its items'
+//            partials in item order),
+//   ss8_run: the 8 squares onto one running sum (k_rmsnorm's order).
+// The contract k_gemv1's forms share (tests/test_gpu_gemm.py pins it): a row of
+// a launch is summed in the ss8 order exactly when a.M * n8 <= Q * NT (n8: items
+// staged per row; Q = 4, gemm.hip GEMV1_Q: the item-per-thread "fast" form holds
+// every item of the block), else in the ss8_run order -- whichever form stages
+// the row, so the row-per-wave forms give the item forms' bits.
+DEV float ss8(bf16x8 v) {
+  float p = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) p += bf(v[j]) * bf(v[j]);
+  return p;
+}
+DEV float ss8_run(float ss, bf16x8 v) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss += bf(v[j]) * bf(v[j]);
+  return ss;
+}
 // Inverse RMS of rows [m0, m0 + nrows) (local index i -> inv_s[i]); same
 // summation order as k_rmsnorm (lane-strided 8-element chunks, wave sum).
 template <class MP = MemPlain>
@@ -104,14 +164,20 @@ DEV void row_inv(const RowMap& am, int M, int K, float eps, int m0, int nrows, f
     float ss = 0.f;
     if (m < M) {
       const bf16* x = rm_bf(am, m);
-      for (int c = lane; c < nch; c += 64) {
-        const bf16x8 v = MP::ld16(x + c * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ss += bf(v[j]) * bf(v[j]);
-      }
+      for (int c = lane; c < nch; c += 64) ss = ss8_run(ss, MP::ld16(x + c * 8));
     }
     ss = wave_sum(ss);
     if (lane == 0) inv_s[i] = rsqrtf(ss / (float)K + eps);
+  }
+}
+// Rows' per-item partial sums part[m * n8 + c] (LDS) -> inv_s[m]: wave w takes
+// rows w, w + NW, ..; its lanes add the row's partials 64 apart, then wave_sum
+DEV void part_inv(const float* part, int n8, int M, int K, float eps, float* inv_s, int wave, int NW, int lane) {
+  for (int m = wave; m < M; m += NW) {
+    float ss = 0.f;
+    for (int c = lane; c < n8; c += 64) ss += part[m * n8 + c];
+    ss = wave_sum(ss);
+    if (lane == 0) inv_s[m] = rsqrtf(ss / (float)K + eps);
   }
 }
 DEV void row_inv(const GemmArgs& a, int m0, int nrows, float* inv_s, int wave, int NW, int lane) {
@@ -123,9 +189,17 @@ DEV void row_inv(const GemmArgs& a, int m0, int nrows, float* inv_s, int wave, i
 DEV float norm_x(bf16 x, float inv) { return rb(bf(x) * inv); }
 DEV float norm_w(float t, bf16 w) { return rb(t * bf(w)); }
 DEV float norm_mod(float t, bf16 sc, bf16 sh) { return rb(rb(t * rb(1.0f + bf(sc))) + bf(sh)); }
+// the chain on one element under runtime (wave-uniform) operand tests: k_gemv1's
+// prologues and xform<XF_NORM> (an absent operand is never read: pass anything)
+DEV bf16 norm_rt(bf16 x, float inv, bool has_w, bf16 w, bool has_mod, bf16 sc, bf16 sh) {
+  float t = norm_x(x, inv);
+  if (has_w) t = norm_w(t, w);
+  if (has_mod) t = norm_mod(t, sc, sh);
+  return tobf(t);
+}
 // the chain on 8 values of a row with inverse RMS inv, the weight / modulation
 // present at compile time (an absent operand is never read: pass anything).
-// xform<XF_NORM> below runs the same steps under GemmArgs' runtime tests: routed
+// xform<XF_NORM> below runs norm_rt's steps under GemmArgs' runtime tests: routed
 // through norm8 (flags as arguments, or a four-way dispatch) k_gemv and k_gemv_w8
 // compiled to other code.
 template <bool HAS_W, bool HAS_MOD>
@@ -153,12 +227,7 @@ DEV bf16x8 xform(const GemmArgs& a, bf16x8 x, int m, int k, float inv) {
       sc = *(const bf16x8*)(md + a.xf.scale_off + k);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = norm_x(x[j], inv);
-      if (a.xf.w) t = norm_w(t, wv[j]);
-      if (md) t = norm_mod(t, sc[j], sh[j]);
-      o[j] = tobf(t);
-    }
+    for (int j = 0; j < 8; ++j) o[j] = norm_rt(x[j], inv, a.xf.w != nullptr, wv[j], md != nullptr, sc[j], sh[j]);
   } else if (XF == XF_SILU_ADD) {
     const bf16x8 v = *(const bf16x8*)(a.xf.vec + k);
 #pragma unroll
@@ -170,6 +239,10 @@ DEV bf16x8 xform(const GemmArgs& a, bf16x8 x, int m, int k, float inv) {
 }
 
 // ------------------------------------------------------------------ epilogues
+// SiLU(gate) * up from the fp32 sums: gate_proj / up_proj outputs, the SiLU and
+// the product are one bf16 rounding each (epi_tile, epi_silu8, the one-launch MLPs)
+DEV bf16 silu_up(float g, float u) { return tobf(rb(silu_f(rb(g))) * rb(u)); }
+
 // One 16(n) x 16(m) MFMA tile in the C/D layout: lane l holds m = m0 + (l & 15),
 // n = n0 + 4*(l >> 4) + i, i = 0..3.  Every lane of the wave must call this
 // (cross-lane exchanges), rows m >= M are dropped inside.
@@ -336,7 +409,7 @@ DEV void epi_row8(const GemmArgs& a, int m, int n, const float v_in[8]) {
 DEV void epi_silu8(const GemmArgs& a, int m, int col, const float gt[8], const float up[8]) {
   bf16x8 o;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = tobf(rb(silu_f(rb(gt[i]))) * rb(up[i]));
+  for (int i = 0; i < 8; ++i) o[i] = silu_up(gt[i], up[i]);
   if (a.epi.pack) {   // act row length N / 2; columns col .. col+7 = one lane's 16 bytes of a block
     const int na = a.N >> 1;
     bf16* p = (bf16*)a.epi.out.base + ((long long)(m >> 4) * (na >> 5) + (col >> 5)) * 512 +
@@ -460,7 +533,7 @@ DEV void epi_tile(const GemmArgs& a, int m, int n0, int lane, const float v_in[4
     const int col = (n0 >> 1) + 4 * g;
     bf16x4 o;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = tobf(rb(silu_f(rb(v[i]))) * rb(u[i]));
+    for (int i = 0; i < 4; ++i) o[i] = silu_up(v[i], u[i]);
     MP::st8(rm_bfw(e.out, m) + col, o);
     return;
   }

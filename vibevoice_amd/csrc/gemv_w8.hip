@@ -58,9 +58,7 @@ constexpr int W8_U = 4;                  // chunk pairs (KB) per batch per wave;
 constexpr int W8_MAX_WAVES = 8;
 constexpr size_t W8_LDS_MAX = 98304;     // A rows staged per K block (dynamic LDS, opt-in above 64 KB)
 
-// the code stream: ldw8 (gemv_dev.h); e4m3 -> bf16: cvt8 (common.h)
-
-DEV int w8_part(int len, int i, int n) { return (int)((unsigned)(len * i) / (unsigned)n); }
+// the code stream: ldw8; the K ranges: k_slice (gemv_dev.h); e4m3 -> bf16: cvt8 (common.h)
 
 // kbp: chunk pairs per K block (host: M * (64 kbp + 8) * 2 bytes of dynamic LDS)
 template <int XF>
@@ -85,7 +83,8 @@ __global__ void __launch_bounds__(64 * W8_MAX_WAVES) k_gemv_w8(GemmArgs a, int k
   for (int pb = 0; pb < npair; pb += kbp) {
     const int np = min(kbp, npair - pb);
     // this wave's chunk pairs [c0, c1) of the block
-    const int c0 = pb + w8_part(np, wave, NW), c1 = pb + w8_part(np, wave + 1, NW);
+    const KRange kr = k_slice(pb, pb + np, wave, NW);
+    const int c0 = kr.c0, c1 = kr.c1;
     const int kw = np * 64, lds_ld = kw + 8, n8 = kw >> 3, ne = a.M * n8;
     u32x4 wa[W8_U] = {zero4, zero4, zero4, zero4}, wb[W8_U] = {zero4, zero4, zero4, zero4};
     // loads past the wave's range are skipped (wave-uniform test): a repeated

@@ -23,7 +23,7 @@
 //     launch's end publishes them).
 // Weights are read with the default cache policy: the head's 170 MB are read S
 // times per token and stay in the Infinity Cache (gemv_dev.h ldw<KEEP>).
-// Arithmetic: persist_dev.h hl_rows_norm (gemv_dev.h norm8) and hl_silu_up,
+// Arithmetic: persist_dev.h hl_rows_norm (gemv_dev.h norm8) and gemv_dev.h silu_up,
 // k_rmsnorm's row order for the norm; the GEMM sums are fp32 MFMA sums in another order than the GEMV
 // kernels', so the layer is within bf16 of the two-launch path, not bitwise
 // (tests/test_gpu_head.py).
@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(hm::NT) k_head_m16(HeadM16Args a) {
       g += red1[(j * 8 + v) * 256 + (c + 16 * (m >> 2)) * 4 + (m & 3)];
       u += red1[(j * 8 + v) * 256 + (c + 8 + 16 * (m >> 2)) * 4 + (m & 3)];
     }
-    su_s[e] = hl_silu_up(g, u);
+    su_s[e] = silu_up(g, u);
   }
   __syncthreads();
   stamp(5, true);

@@ -20,7 +20,7 @@
 //     by DMA into LDS, only this workgroup's 8 rows of each block); issued after
 //     SiLU * up so they stream through the hand-off; MFMA; residual.
 // Arithmetic: persist_dev.h hl_rows_norm (norm weight, no modulation) and
-// hl_silu_up, the residual as epi_row8's EPI_RES; the GEMM sums are fp32 MFMA sums in another
+// silu_up, the residual as epi_row8's EPI_RES; the GEMM sums are fp32 MFMA sums in another
 // order than the GEMV kernels' (tests/test_gpu_lm.py: within bf16 of them).
 //
 // W8 (both kernels' second instantiation; LmFfnArgs::gu8 / gue / dn8 / dne): the
@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(lf::NT) k_lm_ffn(LmFfnArgs a) {
       g += red1[(j * 8 + v) * 256 + (c + 16 * (m >> 2)) * 4 + (m & 3)];
       u += red1[(j * 8 + v) * 256 + (c + 8 + 16 * (m >> 2)) * 4 + (m & 3)];
     }
-    su_s[(j * RMAX + m) * 8 + c] = hl_silu_up(g, u);
+    su_s[(j * RMAX + m) * 8 + c] = silu_up(g, u);
   }
   __syncthreads();
   stamp(4);
@@ -566,7 +566,7 @@ __global__ void __launch_bounds__(lf16::NT) k_lm_ffn16(LmFfnArgs a) {
     const int lg = (c + 16 * (m >> 2)) * 4 + (m & 3), lu = (c + 8 + 16 * (m >> 2)) * 4 + (m & 3);
     const float g = red[(j * 2) * 256 + lg] + red[(j * 2 + 1) * 256 + lg];
     const float u = red[(j * 2) * 256 + lu] + red[(j * 2 + 1) * 256 + lu];
-    su_s[(j * RMAX + m) * 8 + c] = hl_silu_up(g, u);
+    su_s[(j * RMAX + m) * 8 + c] = silu_up(g, u);
   }
   __syncthreads();
   stamp(4);

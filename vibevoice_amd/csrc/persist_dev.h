@@ -110,8 +110,7 @@ DEV void hl_rows_norm(bf16* xs, int XST, int rows, const bf16* nw_s, const bf16*
     *(bf16x8*)(xs + m * XST + c * 8) = o;
   }
 }
-// SiLU(gate) * up from the fp32 sums (gemv_dev.h epi_silu8's rounding points)
-DEV bf16 hl_silu_up(float g, float u) { return tobf(rb(silu_f(rb(g))) * rb(u)); }
+// (SiLU(gate) * up from the fp32 sums: gemv_dev.h silu_up)
 
 // One grid-wide wait: arrival of this workgroup + poll until k waits of this
 // launch have completed.  Lane 0 of the control wave (or of the wave that made
